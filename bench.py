@@ -19,6 +19,16 @@ ids holds exactly the instances a 1-GPU run of the same global batch holds.
 
   python bench.py [--gpus N --steps K --warmup W] [--config C] [--batch B | --global-batch G]
   python bench.py --gpus 2 --dry-run     # CPU/gloo plumbing check of the config-4 path
+  python bench.py --full                 # + everything measured beside the headline figure
+  python bench.py --dump-outputs DIR     # + the last timed step's outputs as DIR/<name>.npy
+
+A plain run sets up, warms up, times the K steps and prints the result line (`roofline` comes
+from HIP events recorded inside the timed steps and costs no run of its own). --full adds, after
+the timed steps: the CPU baseline of the reference pipeline, the end-to-end (PCIe-inclusive) or
+solve-only leg, the single-instance ABI latency, configs 2 and 5 and the N = 16 trot workload,
+and the multi-GPU scaling model. --dump-outputs writes the forces, status codes and iteration
+counts of the last timed step (config 4: the gathered forces) in float32; the same arguments
+give the same inputs in every run.
 
 With --gpus N > 1 and no torchrun environment the script relaunches itself under
 torch.distributed.run (one process per GPU) before touching any GPU. Rank 0 prints ONE JSON
@@ -224,6 +234,33 @@ def abi_latency():
 
 def digest(t) -> str:
     return hashlib.sha256(np.ascontiguousarray(t.cpu().numpy()).tobytes()).hexdigest()[:16]
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs: every file of one run together stays below this
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(path: str, tensors: dict) -> dict:
+    """--dump-outputs: the per-instance arrays the timed path wrote in its last step, one
+    ``path/<name>.npy`` each, float32 (integer outputs converted: status codes and iteration
+    counts are exact in it). The tensors share their leading dimension, one row per instance;
+    where they exceed DUMP_BUDGET_BYTES together, the same fixed, seeded sample of rows of
+    every tensor is written, with the sampled instance indices as ``rows.npy`` (float64)."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    B = next(iter(tensors.values())).shape[0]
+    row_bytes = sum(4 * (t.numel() // B) for t in tensors.values())
+    rows = None
+    if B * row_bytes > DUMP_BUDGET_BYTES:
+        k = DUMP_BUDGET_BYTES // (row_bytes + 8)
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, size=k, replace=False))
+        np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    for name, t in tensors.items():
+        if rows is not None:
+            t = t[torch.from_numpy(rows).to(t.device)]
+        np.save(os.path.join(path, f"{name}.npy"), t.cpu().numpy().astype(np.float32, copy=False))
+    return {"dir": path, "arrays": sorted(tensors), "instances": int(B if rows is None else len(rows)),
+            "sampled": rows is not None}
 
 
 def plumbing_solve(N):
@@ -541,13 +578,22 @@ def main():
     ap.add_argument("--record-format", choices=("compact", "full"), default="compact",
                     help="config 4: the records root holds and sends (compact: trajAll's step-0 row, "
                          "expanded on every rank by cmpc_batch_expand)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip end-to-end / solve-only legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: "
+                         "the CPU baseline, the end-to-end / solve-only legs, the single-instance "
+                         "ABI latency, configs 2 / 5 / N = 16 and the multi-GPU scaling model")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the end-to-end / solve-only legs and the other workloads")
     ap.add_argument("--no-refine", action="store_true",
                     help="A/B only: the wide classes' fp64 refinement off (cmpc_batch_set_refine)")
     ap.add_argument("--dry-run", action="store_true",
                     help="CPU ranks over gloo with a plumbing stand-in for the solve (no GPU)")
     args = ap.parse_args()
+    if not args.full:   # a plain run: set up, warm up, the timed steps, the result line
+        args.no_cpu_baseline = args.no_extras = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(relaunch_distributed(args.gpus))
@@ -639,6 +685,17 @@ def main():
         iters = leg["iters"]
         recs = leg["recs"]
         B_total, B_local = B * world, B
+
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left in the caller's buffers (rank 0's; config 4: the gathered
+        # forces of the whole batch), read before any --full leg runs the solver again
+        sync()
+        if config == 4:
+            outs = {"forces": pipe.forces}
+        else:
+            outs = {"forces": forces, "status": status, "iters": iters}
+        dumped = dump_outputs(args.dump_outputs, outs)
 
     # ---- untimed extras -------------------------------------------------------------------
     launch_ms, ovf = (timed.read_timing() if timed is not None else (np.zeros((0, 2)), 0))
@@ -761,6 +818,8 @@ def main():
     }
     if getattr(args, "no_refine", False):
         out["config"]["refine"] = "off (A/B run, cmpc_batch_set_refine(0): not the product setting)"
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if args.dry_run:
         out["dry_run"] = "gloo CPU ranks, plumbing stand-in for the solve (not a measurement)"
     out.update(extras)

@@ -18,7 +18,7 @@ if [ $TESTS = 1 ]; then
   rc=$?
   echo "pytest rc=$rc"; grep -E "FAILED|passed|failed" $OUT/pytest.log | tail -30
   [ $rc -le 1 ] || exit 1
-  timeout -k 10 400 python -u bench.py > $OUT/bench.log 2>&1 || { echo bench failed; tail -5 $OUT/bench.log; exit 1; }
+  timeout -k 10 400 python -u bench.py --full > $OUT/bench.log 2>&1 || { echo bench failed; tail -5 $OUT/bench.log; exit 1; }
   python3 scripts/bench_summary.py $OUT/bench.log
 fi
 if [ $PROBE = 1 ]; then
