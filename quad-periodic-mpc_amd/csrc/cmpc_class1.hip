@@ -214,6 +214,25 @@ __device__ __forceinline__ void pin(float (&x)[M]) {
   for (int c = 0; c < M; c++) asm volatile("" : "+v"(x[c]));
 }
 
+// Element q (LO <= q < HI, wave-uniform: an SGPR) of a register-resident row, as a tree of scalar
+// branches on q with one v_mov at its leaf: no LDS traffic and almost no VALU. The opaque leaf keeps
+// the optimiser from folding the branches into v_cndmask selects (HI - LO - 1 of them: measured
+// slower). x[q] with a dynamic index would send the row to scratch, and so would a
+// select between two elements' addresses.
+template <int LO, int HI, int MA>
+__device__ __forceinline__ float pick_col(const float (&x)[MA], int q) {
+  static_assert(0 <= LO && LO < HI && HI <= MA, "column range");
+  if constexpr (HI - LO == 1) {
+    float r = x[LO];
+    asm volatile("" : "+v"(r));
+    return r;
+  } else {
+    constexpr int MID = (LO + HI) / 2;
+    if (q < MID) return pick_col<LO, MID>(x, q);
+    return pick_col<MID, HI>(x, q);
+  }
+}
+
 // Scheduling fence inside long unrolled LDS->FMA sweeps: without it the scheduler issues every
 // ds_read_b128 of a row up front (64 extra live VGPRs on top of the 65-slot row).
 #ifndef CMPC_FENCE_COLS
@@ -791,19 +810,21 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       sh.vbuf()[v] = dm;
       lsync();
       // z = J2 d2 (primal step direction), zn = |d2|^2 = z' n+, dn = |d|^2
-      f2v zacc = {0.f, 0.f}, nacc = {0.f, 0.f};
+      // d sits one element per lane: both norms are lane reductions, issued ahead of the z sweep
+      // so that they run under its loads
+      const float dn = wave_sum((v < n) ? dv * dv : 0.f);
+      const float zn = wave_sum(dm * dm);
+      f2v zacc = {0.f, 0.f};
       piped_sweep<0, NV, C1_PIPE_GRP>(
           [&](auto C) { return *reinterpret_cast<const float4*>(&sh.vbuf()[decltype(C)::value]); },
           [&](auto C, float4 m4) {
             constexpr int c = decltype(C)::value;
             C1_DOT(zacc, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3], m4);
-            C1_DOT(nacc, m4.x, m4.y, m4.z, m4.w, m4);
           });
-      float zv = zacc.x + zacc.y, zn = nacc.x + nacc.y;
-      // materialise both sums here: otherwise the FMAs sink below the back substitution loop
-      // and the NV loaded values of vbuf stay live across it (158 VGPRs, three waves per SIMD)
-      asm volatile("" : "+v"(zv), "+v"(zn));
-      const float dn = wave_sum((v < n) ? dv * dv : 0.f);
+      float zv = zacc.x + zacc.y;
+      // materialise the sum here: otherwise the FMAs sink below the back substitution loop and
+      // the NV loaded values of vbuf stay live across it (158 VGPRs, three waves per SIMD)
+      asm volatile("" : "+v"(zv));
       C1_SUB(1);
       // r = R^-1 d1 (lane i ends with r_i). While R^-1 is kept (every step so far an add, q <=
       // QI) it is a matvec over its packed columns: no dependent chain, four columns per trip.
@@ -862,7 +883,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       C1_SUB(2);
       const bool add = !zero_step && t2 <= t1;
       const bool add_u = __builtin_amdgcn_readfirstlane((int)add) != 0;
-      float beta = 0.f;
+      float beta = 0.f, sigma = 0.f;  // w = d2 + sigma e_q
       if (add) {
         // ---- add p: the Householder reflection I - beta w w' on columns q..n-1 maps
         // d[q..n-1] to -sgn(d_q) |d[q..n-1]| e_q; R gains the column (d[0..q-1], -sgn ts)
@@ -870,6 +891,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
         const float dq = rl(dv, q);
         const float sgn = (dq >= 0.f) ? 1.f : -1.f;
         beta = fast_rcp(ts * (ts + fabsf(dq)));  // 2 / (w'w)
+        sigma = sgn * ts;
         sh.vbuf()[v] = (v == q) ? dq + sgn * ts : dm;
         const int offq = rcol(q);
         if (v < q) sh.P[offq + v] = dv;
@@ -956,18 +978,11 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       // spilled VGPRs); the Givens chain only on a drop (add_u is wave-uniform; the branch leaves
       // the register allocation unchanged, same instruction count).
       {
-        // J <- J (I - beta w w'): tw = J_v . w, J_v -= beta tw w  (no-op on a drop: beta = 0)
-        f2v tacc = {0.f, 0.f};
-        piped_sweep<0, NV, C1_PIPE_GRP>(
-            [&](auto C) { return *reinterpret_cast<const float4*>(&sh.vbuf()[decltype(C)::value]); },
-            [&](auto C, float4 w4) {
-              constexpr int c = decltype(C)::value;
-              C1_DOT(tacc, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3], w4);
-            });
-        const float bt = -beta * (tacc.x + tacc.y);
-        // re-read w from LDS: without this point the compiler keeps all NV values of the first
-        // sweep's loads live for the second (a whole row of extra VGPRs)
-        asm volatile("" ::: "memory");
+        // J <- J (I - beta w w'): tw = J_v . w, J_v -= beta tw w  (no-op on a drop: beta = 0).
+        // w = d2 + sigma e_q and z_v = J_v . d2 is this trip's z: tw = z_v + sigma J[v][q], one
+        // column pick (scalar branches on q) and one FMA instead of a second row-long dot product
+        const int qs = __builtin_amdgcn_readfirstlane(q);
+        const float bt = -beta * fmaf(sigma, pick_col<0, NV>(slot, qs), zv);
         piped_sweep<0, NV, C1_PIPE_GRP>(
             [&](auto C) { return *reinterpret_cast<const float4*>(&sh.vbuf()[decltype(C)::value]); },
             [&](auto C, float4 w4) {
