@@ -313,6 +313,8 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
   Model md;
   make_model(srec, P.dt, md);
   make_bdt<64>(srec, md, v, sh.u.BdtT);
+  CondGeo cg;
+  make_cond_geo<true>(srec, md, cg);
   lsync();
   if (v < N) {
     float e[13];
@@ -373,12 +375,13 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       const float k = (float)(i - kv);
       const float k2 = 0.5f * k * (k - 1.f);
       float gk[13];
+      col_power(b, u1, u2, k, k2, gk);
 #pragma unroll
-      for (int j = 0; j < 13; j++) gk[j] = act ? fmaf(k2, u2[j], fmaf(k, u1[j], b[j])) : 0.f;
+      for (int j = 0; j < 13; j++) gk[j] = act ? gk[j] : 0.f;
       recur(md, wts, gk, z);
-      asm volatile("" ::: "memory");  // the Bdt column loads stay inside the step
+      asm volatile("" ::: "memory");  // the step's LDS traffic stays inside the step
       const int wb = __builtin_amdgcn_readfirstlane(sh.blkbase[i]);
-      step_columns(sh.u.BdtT, step_mask(msk0, msk1, i), wb, z, [&](int w, float val) {
+      step_entries(md, cg, sh.u.BdtT, step_mask(msk0, msk1, i), wb, z, [&](int w, float val) {
         if (w == v) val += P.alpha2;  // qH = 2 (B'SB + alpha I), SolverMPC.cpp:806
         if (act && w >= v) sh.P[myrow + w] = val;
       });

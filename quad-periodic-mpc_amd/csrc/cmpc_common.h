@@ -289,15 +289,131 @@ __device__ __forceinline__ unsigned step_mask(unsigned long long m0, unsigned lo
   return (unsigned)(((i < 16) ? (m0 >> (4 * i)) : (m1 >> (4 * i - 64))) & 15ull);
 }
 
+// ---------------------------------------------------------------------------------------------
+// H entries from Bdt's structure. Column c = 3 f + a of Bdt (make_bdt below) is, with
+// T_f = I_world^-1 [r_f]x and im = 1/m,
+//   rows 0..2: dt^2/2 R' T_f[:,a]      rows 3+a: dt^2/2 im  (a = 0: row 5 += dt^3/6 x_drag im)
+//   rows 6..8: dt T_f[:,a]             rows 9+a: dt im      (a = 0: row 11 += dt^2/2 x_drag im)
+// so 2 b_c' z = 2 T_f[:,a]' q + 2 p_a with q = dt z[6..8] + dt^2/2 R z[0..2] and
+// T_f[:,a]' q = ([r_f]x' I_world^-T q)_a = (w x r_f)_a, w = I_world^-T q: one projection (w, p) per
+// step and row, shared by every foot, and two FMAs per entry with nothing loaded per entry
+// (DESIGN.md §4.1). CMPC_COND_DOT13 = 1 keeps the per-entry 13-term dot product with the Bdt
+// column from LDS (A/B builds).
+// ---------------------------------------------------------------------------------------------
+#ifndef CMPC_COND_DOT13
+#define CMPC_COND_DOT13 0
+#endif
+
+// what the entries need of the instance besides the model: I_world^-1 and the foot positions
+// (uniform over the instance)
+struct CondGeo {
+  float Ii[9];   // I_world^-1, row-major
+  float r[12];   // r[4 i + f]: component i of foot f (the record's layout)
+};
+// per step and row: w and p above, both doubled (the 2 of qH = 2 B'SB)
+struct StepProj {
+  float w[3], p[3];
+};
+
+// I_world^-1 = (R I_body R')^-1 by cofactors; m = 12 RobotState.h:26,
+// I_body = diag(.07, .26, .242) RobotState.h:25, I_world = R I_body R^T SolverMPC.cpp:593
+__device__ __forceinline__ void make_iinv(const Model& md, float* Ii) {
+  const float Ib0 = .07f, Ib1 = 0.26f, Ib2 = 0.242f;
+  float Iw[9];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int j = 0; j < 3; j++)
+      Iw[i * 3 + j] = md.R[i * 3 + 0] * Ib0 * md.R[j * 3 + 0] + md.R[i * 3 + 1] * Ib1 * md.R[j * 3 + 1] +
+                      md.R[i * 3 + 2] * Ib2 * md.R[j * 3 + 2];
+  const float c00 = Iw[4] * Iw[8] - Iw[5] * Iw[7];
+  const float c10 = Iw[5] * Iw[6] - Iw[3] * Iw[8];
+  const float c20 = Iw[3] * Iw[7] - Iw[4] * Iw[6];
+  const float idet = 1.f / (Iw[0] * c00 + Iw[1] * c10 + Iw[2] * c20);
+  Ii[0] = c00 * idet; Ii[1] = (Iw[2] * Iw[7] - Iw[1] * Iw[8]) * idet; Ii[2] = (Iw[1] * Iw[5] - Iw[2] * Iw[4]) * idet;
+  Ii[3] = c10 * idet; Ii[4] = (Iw[0] * Iw[8] - Iw[2] * Iw[6]) * idet; Ii[5] = (Iw[2] * Iw[3] - Iw[0] * Iw[5]) * idet;
+  Ii[6] = c20 * idet; Ii[7] = (Iw[1] * Iw[6] - Iw[0] * Iw[7]) * idet; Ii[8] = (Iw[0] * Iw[4] - Iw[1] * Iw[3]) * idet;
+}
+
+// every lane gets the instance's I_world^-1 and foot positions (the same arithmetic as make_bdt's
+// lanes, so both forms see one matrix). UNIFORM: the whole workgroup works on one instance, and
+// the 21 values move to SGPRs, where they cost the entry loop no VGPR.
+template <bool UNIFORM, typename RecPtr>
+__device__ __forceinline__ void make_cond_geo(RecPtr rec, const Model& md, CondGeo& cg) {
+  make_iinv(md, cg.Ii);
+#pragma unroll
+  for (int j = 0; j < 12; j++) cg.r[j] = rec[CMPC_REC_R + j];
+  if constexpr (UNIFORM) {
+#pragma unroll
+    for (int j = 0; j < 9; j++) cg.Ii[j] = rfl(cg.Ii[j]);
+#pragma unroll
+    for (int j = 0; j < 12; j++) cg.r[j] = rfl(cg.r[j]);
+  }
+}
+
+// the step's projection of z
+__device__ __forceinline__ void step_proj(const Model& md, const CondGeo& cg, const float* z, StepProj& pj) {
+  const float dt2 = 2.f * md.dt, dtq = 2.f * md.dth, dtc = md.dt * md.dt * md.dt / 3.f;  // 2 dt, 2 dt^2/2, 2 dt^3/6
+  const float im = 1.f / 12.0f;
+  float q[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+    q[i] = fmaf(dt2, z[6 + i], dtq * fmaf(md.R[i * 3 + 2], z[2], fmaf(md.R[i * 3 + 1], z[1], md.R[i * 3] * z[0])));
+#pragma unroll
+  for (int j = 0; j < 3; j++)  // I_world^-T q: the transpose spelled out, no symmetry assumed of the rounded matrix
+    pj.w[j] = fmaf(cg.Ii[6 + j], q[2], fmaf(cg.Ii[3 + j], q[1], cg.Ii[j] * q[0]));
+#pragma unroll
+  for (int a = 0; a < 3; a++) pj.p[a] = im * fmaf(dt2, z[9 + a], dtq * z[3 + a]);
+  pj.p[0] = fmaf(im * md.xdrag, fmaf(dtq, z[11], dtc * z[5]), pj.p[0]);
+}
+
+// foot f's three entries 2 b_c' z, c = 3 f .. 3 f + 2, from the projection: (w x r_f) + p
+__device__ __forceinline__ void foot_entries(const StepProj& pj, float r0, float r1, float r2, float* out) {
+  out[0] = fmaf(pj.w[1], r2, fmaf(-pj.w[2], r1, pj.p[0]));
+  out[1] = fmaf(pj.w[2], r0, fmaf(-pj.w[0], r2, pj.p[1]));
+  out[2] = fmaf(pj.w[0], r1, fmaf(-pj.w[1], r0, pj.p[2]));
+}
+
+// Column power e = Adt^k b = b + k u1 + k (k - 1)/2 u2 (k2 = k (k - 1)/2) for a column b of Bdt,
+// u1 = N1 b, u2 = N1 u1. n1_mul zeroes rows 6..10 and 12, so u1 is nonzero in rows 0..5 and 11
+// only and u2 in row 5 only; the other terms are written out (fma(k, 0, x) is x for finite k, but
+// the compiler may not fold it).
+__device__ __forceinline__ void col_power(const float* b, const float* u1, const float* u2, float k, float k2,
+                                          float* e) {
+#pragma unroll
+  for (int j = 0; j < 5; j++) e[j] = fmaf(k, u1[j], b[j]);
+  e[5] = fmaf(k2, u2[5], fmaf(k, u1[5], b[5]));
+#pragma unroll
+  for (int j = 6; j < 11; j++) e[j] = b[j];
+  e[11] = fmaf(k, u1[11], b[11]);
+  e[12] = b[12];
+}
+
 // The H entries of horizon step i for one row: for every stance foot f of the step (uniform
 // mask mi, ascending) and axis a, column c = 3 f + a of Bdt lands at reduced column
 // w = wb + 3 rank(f) + a with value 2 b_c' z. Unrolled over the 4 feet x 3 axes with uniform
-// branches: the Bdt columns are broadcast LDS reads at constant addresses, with no
-// column-id -> column dependent-load chain (the dynamic loop over the step's columns waited on
-// two LDS round trips per column). st(w, val) stores the entry.
+// branches, no column-id -> column dependent-load chain (the dynamic loop over the step's columns
+// waited on two LDS round trips per column). st(w, val) stores the entry.
 template <class St>
-__device__ __forceinline__ void step_columns(const float (*BdtT)[16], unsigned mi, int wb,
-                                             const float* z, St&& st) {
+__device__ __forceinline__ void step_columns(const CondGeo& cg, unsigned mi, int wb, const StepProj& pj,
+                                             St&& st) {
+  int w = wb;
+  static_for<0, 4>([&](auto F) {
+    constexpr int f = decltype(F)::value;
+    if (mi & (1u << f)) {
+      float val[3];
+      foot_entries(pj, cg.r[f], cg.r[4 + f], cg.r[8 + f], val);
+      st(w, val[0]);
+      st(w + 1, val[1]);
+      st(w + 2, val[2]);
+      w += 3;
+    }
+  });
+}
+// the same by the 13-term dot products: the Bdt columns are broadcast LDS reads at constant addresses
+template <class St>
+__device__ __forceinline__ void step_columns_dot13(const float (*BdtT)[16], unsigned mi, int wb,
+                                                   const float* z, St&& st) {
   int w = wb;
   static_for<0, 4>([&](auto F) {
     constexpr int f = decltype(F)::value;
@@ -315,6 +431,18 @@ __device__ __forceinline__ void step_columns(const float (*BdtT)[16], unsigned m
       });
     }
   });
+}
+// one step of one row in either form
+template <class St>
+__device__ __forceinline__ void step_entries(const Model& md, const CondGeo& cg, const float (*BdtT)[16],
+                                             unsigned mi, int wb, const float* z, St&& st) {
+#if CMPC_COND_DOT13
+  step_columns_dot13(BdtT, mi, wb, z, st);
+#else
+  StepProj pj;
+  step_proj(md, cg, z, pj);
+  step_columns(cg, mi, wb, pj, st);
+#endif
 }
 
 // quaternion (w,x,y,z) -> rotation matrix, as Eigen's toRotationMatrix (RobotState.cpp:36)
@@ -347,22 +475,8 @@ __device__ __forceinline__ void make_bdt(const float* __restrict__ rec, const Mo
                                          float (*BdtT)[16]) {
   static_assert(NT >= 12, "one thread per force column");
   if (tid < 12) {
-    const float Ib0 = .07f, Ib1 = 0.26f, Ib2 = 0.242f;
-    float Iw[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++)
-        Iw[i * 3 + j] = md.R[i * 3 + 0] * Ib0 * md.R[j * 3 + 0] + md.R[i * 3 + 1] * Ib1 * md.R[j * 3 + 1] +
-                        md.R[i * 3 + 2] * Ib2 * md.R[j * 3 + 2];
-    const float c00 = Iw[4] * Iw[8] - Iw[5] * Iw[7];
-    const float c10 = Iw[5] * Iw[6] - Iw[3] * Iw[8];
-    const float c20 = Iw[3] * Iw[7] - Iw[4] * Iw[6];
-    const float idet = 1.f / (Iw[0] * c00 + Iw[1] * c10 + Iw[2] * c20);
     float Ii[9];
-    Ii[0] = c00 * idet; Ii[1] = (Iw[2] * Iw[7] - Iw[1] * Iw[8]) * idet; Ii[2] = (Iw[1] * Iw[5] - Iw[2] * Iw[4]) * idet;
-    Ii[3] = c10 * idet; Ii[4] = (Iw[0] * Iw[8] - Iw[2] * Iw[6]) * idet; Ii[5] = (Iw[2] * Iw[3] - Iw[0] * Iw[5]) * idet;
-    Ii[6] = c20 * idet; Ii[7] = (Iw[1] * Iw[6] - Iw[0] * Iw[7]) * idet; Ii[8] = (Iw[0] * Iw[4] - Iw[1] * Iw[3]) * idet;
+    make_iinv(md, Ii);
     const float im = 1.f / 12.0f;
     const float dt = md.dt, dt2 = md.dth, dt3 = md.dt * md.dt * md.dt / 6.f;
     const int c = tid;

@@ -28,6 +28,8 @@ __device__ void condense_one(const float* __restrict__ rec, const KParams& P, Sh
   Model md;
   make_model(rec, P.dt, md);
   make_bdt<NTG>(rec, md, tid, sh.BdtT);
+  CondGeo cg;
+  make_cond_geo<true>(rec, md, cg);
   __syncthreads();
   if (tid < N) {
     float e[13];
@@ -77,21 +79,19 @@ __device__ void condense_one(const float* __restrict__ rec, const KParams& P, Sh
       const float k = (float)(i - kv);
       const float k2 = 0.5f * k * (k - 1.f);
       float gk[13];
-#pragma unroll
-      for (int j = 0; j < 13; j++) gk[j] = fmaf(k2, u2[j], fmaf(k, u1[j], b[j]));
+      col_power(b, u1, u2, k, k2, gk);
       recur(md, wts, gk, z);
-      for (int w = max(12 * i, v); w < 12 * i + 12; w++) {
-        float bw[13];
-#pragma unroll
-        for (int j = 0; j < 13; j++) bw[j] = sh.BdtT[w - 12 * i][j];
-        float val = 2.f * dot13(bw, z);
+      // every foot-step is kept: all four feet, columns 12 i .. 12 i + 11 (the solvers' entry form)
+      step_entries(md, cg, sh.BdtT, 15u, 12 * i, z, [&](int w, float val) {
         if (w == v) val += P.alpha2;  // qH = 2 (B'SB + alpha I), SolverMPC.cpp:806
 #ifdef CMPC_DIAG_PERTURB  // diagnostic builds only: a deliberately wrong qH (shows the parity gate fails)
         val *= 1.f + CMPC_DIAG_PERTURB;
 #endif
-        H[(size_t)v * n + w] = val;
-        H[(size_t)w * n + v] = val;
-      }
+        if (w >= v) {
+          H[(size_t)v * n + w] = val;
+          H[(size_t)w * n + v] = val;
+        }
+      });
     }
   }
 }

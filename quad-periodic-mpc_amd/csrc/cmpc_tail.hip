@@ -24,6 +24,14 @@
 //     pair. Active-set positions stay in lanes (q <= 64); an instance whose active set would grow
 //     past 64 positions is handed to the 80-column wide class (ovf list), which solves it afresh.
 // Everything is fp32 (the reference condenses in fp32: common_types.h:14).
+
+// The tail class keeps the H entries as 13-term dot products with the Bdt columns: with the
+// entries from Bdt's structure (cmpc_common.h, CMPC_COND_DOT13 = 0) its scratch rose from
+// 24 / 44 / 44 to 24 / 52 / 60-64 B per lane at the 168-VGPR cap, with I_world^-1 and the feet in
+// SGPRs or in VGPRs alike.
+#ifndef CMPC_COND_DOT13
+#define CMPC_COND_DOT13 1
+#endif
 #include "cmpc_common.h"
 
 #ifndef CMPC_TAIL_WAVES_PER_EU
@@ -265,6 +273,8 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
 
   // ---- condensation: lane v builds H[v][w], w >= v, into the packed triangle (class 1's
   // recursion); lanes v < T then build the tail rows 64 + v over the last steps
+  CondGeo cg;  // (unused, and removed as dead code, in the 13-term form)
+  make_cond_geo<true>(srec, md, cg);
   float gv;
   {
     const int kv = sh.varblk[v];
@@ -301,12 +311,13 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
       const float k = (float)(i - kv);
       const float k2 = 0.5f * k * (k - 1.f);
       float gk[13];
+      col_power(b, u1, u2, k, k2, gk);
 #pragma unroll
-      for (int j = 0; j < 13; j++) gk[j] = act ? fmaf(k2, u2[j], fmaf(k, u1[j], b[j])) : 0.f;
+      for (int j = 0; j < 13; j++) gk[j] = act ? gk[j] : 0.f;
       recur(md, wts, gk, z);
       asm volatile("" ::: "memory");
       const int wb = __builtin_amdgcn_readfirstlane(sh.blkbase[i]);
-      step_columns(sh.u.BdtT, step_mask(msk0, msk1, i), wb, z, [&](int w, float val) {
+      step_entries(md, cg, sh.u.BdtT, step_mask(msk0, msk1, i), wb, z, [&](int w, float val) {
         if (w == v) val += P.alpha2;  // qH = 2 (B'SB + alpha I), SolverMPC.cpp:806
         if (act && w >= v) sh.P[myrow + w] = val;
       });
@@ -333,12 +344,13 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
       const float k = (float)(i - kv);
       const float k2 = 0.5f * k * (k - 1.f);
       float gk[13];
+      col_power(b, u1, u2, k, k2, gk);
 #pragma unroll
-      for (int j = 0; j < 13; j++) gk[j] = act ? fmaf(k2, u2[j], fmaf(k, u1[j], b[j])) : 0.f;
+      for (int j = 0; j < 13; j++) gk[j] = act ? gk[j] : 0.f;
       recur(md, wts, gk, z);
       asm volatile("" ::: "memory");
       const int wb = __builtin_amdgcn_readfirstlane(sh.blkbase[i]);
-      step_columns(sh.u.BdtT, step_mask(msk0, msk1, i), wb, z, [&](int w, float val) {
+      step_entries(md, cg, sh.u.BdtT, step_mask(msk0, msk1, i), wb, z, [&](int w, float val) {
         if (w == r) val += P.alpha2;
         if (act && w >= r) sh.P[myrow + w] = val;
       });
