@@ -242,6 +242,48 @@ CMPC_EXTERNC int cmpc_batch_expand(cmpc_batch* h, const float* d_compact, float*
 /* Same, host buffers in and out (H2D + solve + D2H on the handle's stream, synchronous). */
 CMPC_EXTERNC int cmpc_batch_solve_host(cmpc_batch* h, const float* records, int batch,
                                        float* forces, uint8_t* status, int32_t* iters);
+/* Prediction, cost and optimality gap of given forces U [batch * 12N] (this solver's, qpOASES's,
+ * ADMM's or the caller's own), in fp64, against the exact QP the fp32 record defines: the model
+ * matrices in fp64 from the record's fp32 words, Adt / Bdt / Qdt = the exact exponential (A_c^3 =
+ * 0), no H or g formed. New API.
+ *   x_k+1 = Adt x_k + Bdt u_k + Qdt f,  x_0 = [rpy, p, w, v, -9.8] (rpy = quat_to_rpy of q rounded
+ *           to fp32, SolverMPC.cpp:352-361, 592), f = (0,0,0,f_est3,0,0) if flag bit 0, else 0
+ *   cost  = sum_k (x_k - xd_k)' W (x_k - xd_k) + alpha |U|^2,  W = diag(weights, 0), k = 1..N
+ *   cost0 = the same at U = 0;  cost - cost0 = 1/2 U'HU + g'U, the reference's QP objective
+ *   grad  = HU + g by the adjoint: lambda <- Adt' lambda + 2 W e_k, grad_k = Bdt' lambda + 2 alpha u_k
+ *   gap   = sum over stance foot-steps of  grad_fs . f_fs - min(0, ub (grad_z - mu |grad_x| - mu |grad_y|))
+ * with ub = gait x f_max and 1/mu as fmat holds it in fp32 (SolverMPC.cpp:657-665); a foot-step is
+ * stance unless |ub| < 0.01 (SolverMPC.cpp:869-894). The feasible set is a product of truncated
+ * pyramids {|fx| <= mu fz, |fy| <= mu fz, 0 <= fz <= ub} with vertices 0 and (+-mu ub, +-mu ub, ub),
+ * so gap is the Frank-Wolfe gap in closed form: for feasible U, cost(U) - cost(U*) <= gap, and
+ * gap = 0 at the optimum; no active-set tolerance, no multipliers. (Strong convexity also gives
+ * |U - U*|_2 <= sqrt(gap / alpha), which at alpha ~ 4e-5 is newtons wide: not a useful distance.)
+ * Outputs, either may be NULL (not both):
+ *   d_xpred [batch * 12N] fp32: x_1 .. x_N rounded from fp64, step-major, components in the order
+ *           of the record's traj rows (rpy, p, w, v);
+ *   d_cert  [batch * CMPC_CERT_WORDS] fp64, indexed by CMPC_CERT_*.
+ * Non-finite input gives NaN words. Asynchronous on the handle's stream. Returns 0 or a negative
+ * error: bad batch, both outputs NULL, or a handle that keeps fewer than N output steps
+ * (cmpc_batch_set_output_steps: its forces are not a full solution). */
+#define CMPC_CERT_COST    0   /* cost(U)                                                         */
+#define CMPC_CERT_COST0   1   /* cost(0)                                                         */
+#define CMPC_CERT_GAP     2   /* Frank-Wolfe gap (>= cost(U) - cost(U*) for feasible U)         */
+#define CMPC_CERT_VIOL    3   /* max over stance foot-steps of the negative slack of the rows   */
+                              /* (+-fx/mu + fz)/sqrt(1/mu^2 + 1), (+-fy/mu + fz)/sqrt(1/mu^2 + 1), */
+                              /* fz, ub - fz; clamped at 0                                        */
+#define CMPC_CERT_SWING   4   /* max |f| over swing foot-steps                                   */
+#define CMPC_CERT_GRADMAX 5   /* max |grad| over stance columns                                  */
+#define CMPC_CERT_WORDS   8   /* words 6, 7: padding, written as 0                               */
+CMPC_EXTERNC int cmpc_batch_evaluate(cmpc_batch* h, const float* d_records, const float* d_forces,
+                                     int batch, float* d_xpred, double* d_cert);
+/* Same, host buffers in and out (H2D + kernel + D2H on the handle's stream, synchronous). */
+CMPC_EXTERNC int cmpc_batch_evaluate_host(cmpc_batch* h, const float* records, const float* forces,
+                                          int batch, float* xpred, double* cert);
+/* Single-instance surface: cmpc_batch_evaluate of the record and the solution of the last
+ * update_problem_data* call (x_pred [12N] fp32, cert [CMPC_CERT_WORDS] fp64; either may be NULL).
+ * Runs on request only, so the reference protocol's latency is untouched. Returns a negative
+ * error before the first solve. New API. */
+CMPC_EXTERNC int cmpc_evaluate_last(float* x_pred, double* cert);
 /* Parity hook for the condensation rows (SolverMPC.cpp:96-146, 806-814): full 12N x 12N qH
  * (row-major) and qg per instance, all variables kept (no swing elimination). */
 CMPC_EXTERNC int cmpc_batch_condense(cmpc_batch* h, const float* d_records, int batch,

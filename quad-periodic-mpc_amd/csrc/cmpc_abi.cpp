@@ -56,6 +56,9 @@ struct cmpc_batch {
   int* d_one = nullptr;
   float* d_single_out = nullptr;
   float* h_pin = nullptr;
+  // outputs of cmpc_batch_evaluate_host (allocated on its first call, sized max_batch)
+  float* d_xpred = nullptr;
+  double* d_cert = nullptr;
   // side streams + fork/join events for the wider size classes (cmpc_launch.hip)
   cmpc::LaunchCtx ctx;
   bool pooled_sides = false;     // ctx.side came from the process-wide pool (acquire_sides)
@@ -465,6 +468,10 @@ static void free_staging(cmpc_batch* h) {
   if (h->d_one) (void)hipFree(h->d_one);
   if (h->d_single_out) (void)hipFree(h->d_single_out);
   if (h->h_pin) (void)hipHostFree(h->h_pin);
+  if (h->d_xpred) (void)hipFree(h->d_xpred);
+  if (h->d_cert) (void)hipFree(h->d_cert);
+  h->d_xpred = nullptr;
+  h->d_cert = nullptr;
   h->d_rec = h->d_forces = h->d_admm_H = h->d_single_out = h->h_pin = nullptr;
   h->d_status = nullptr;
   h->d_iters = nullptr;
@@ -587,6 +594,68 @@ extern "C" int cmpc_batch_solve_host(cmpc_batch* h, const float* records, int ba
   return 0;
 }
 
+extern "C" int cmpc_batch_evaluate(cmpc_batch* h, const float* d_records, const float* d_forces, int batch,
+                                   float* d_xpred, double* d_cert) {
+  if (!h || batch < 0 || batch > h->max_batch || (batch && (!d_records || !d_forces))) {
+    g_last_error = "cmpc_batch_evaluate: bad arguments";
+    return -1;
+  }
+  if (!d_xpred && !d_cert) {
+    g_last_error = "cmpc_batch_evaluate: both outputs are NULL";
+    return -1;
+  }
+  if (h->kp.out_cols != 12 * h->prm.horizon) {
+    g_last_error = "cmpc_batch_evaluate: the handle keeps fewer than N output steps, its forces are not a full solution";
+    return -3;
+  }
+  const hipError_t e = cmpc::launch_evaluate(d_records, d_forces, batch, h->kp, (double)h->prm.alpha, d_xpred,
+                                             d_cert, h->stream);
+  if (e != hipSuccess) return fail("launch_evaluate", e);
+  return 0;
+}
+
+extern "C" int cmpc_batch_evaluate_host(cmpc_batch* h, const float* records, const float* forces, int batch,
+                                        float* xpred, double* cert) {
+  if (!h || batch < 0 || batch > h->max_batch || (batch && (!records || !forces))) {
+    g_last_error = "cmpc_batch_evaluate_host: bad arguments";
+    return -1;
+  }
+  if (!xpred && !cert) {
+    g_last_error = "cmpc_batch_evaluate_host: both outputs are NULL";
+    return -1;
+  }
+  if (h->kp.out_cols != 12 * h->prm.horizon) {
+    g_last_error = "cmpc_batch_evaluate_host: the handle keeps fewer than N output steps";
+    return -3;
+  }
+  if (batch == 0) return 0;
+  if (int r = ensure_staging(h)) return r;
+  hipError_t e;
+  if (!h->d_xpred && (e = hipMalloc(&h->d_xpred, (size_t)12 * CMPC_MAX_HORIZON * h->max_batch * sizeof(float))) != hipSuccess) {
+    h->d_xpred = nullptr;
+    return fail("hipMalloc(x_pred)", e);
+  }
+  if (!h->d_cert && (e = hipMalloc(&h->d_cert, (size_t)CMPC_CERT_WORDS * h->max_batch * sizeof(double))) != hipSuccess) {
+    h->d_cert = nullptr;
+    return fail("hipMalloc(cert)", e);
+  }
+  const int N = h->prm.horizon;
+  const size_t rw = (size_t)CMPC_REC_WORDS(N);
+  if ((e = hipMemcpyAsync(h->d_rec, records, rw * batch * sizeof(float), hipMemcpyHostToDevice, h->stream)) != hipSuccess)
+    return fail("H2D", e);
+  if ((e = hipMemcpyAsync(h->d_forces, forces, sizeof(float) * 12 * N * batch, hipMemcpyHostToDevice, h->stream)) != hipSuccess)
+    return fail("H2D", e);
+  if (int r = cmpc_batch_evaluate(h, h->d_rec, h->d_forces, batch, xpred ? h->d_xpred : nullptr,
+                                  cert ? h->d_cert : nullptr))
+    return r;
+  if (xpred && (e = hipMemcpyAsync(xpred, h->d_xpred, sizeof(float) * 12 * N * batch, hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
+    return fail("D2H", e);
+  if (cert && (e = hipMemcpyAsync(cert, h->d_cert, sizeof(double) * CMPC_CERT_WORDS * batch, hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
+    return fail("D2H", e);
+  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
+  return 0;
+}
+
 // =============================================================================================
 // Reference single-instance interface (convexMPC_interface.cpp + the solve_mpc globals).
 // =============================================================================================
@@ -618,6 +687,7 @@ struct SingleState {
   // solve_mpc state
   std::vector<double> q_soln;
   int has_solved = 0;
+  bool eval_ok = false;           // h->d_rec holds the record q_soln solves (cmpc_evaluate_last)
   cmpc_batch* h = nullptr;
   int h_horizon = -1;
   // periodic-disturbance estimator state (SolverMPC.cpp:390-398, 555-563, 688-798): histories,
@@ -711,6 +781,7 @@ int solve_single_device(SingleState& s, const float* rec, int N, float* forces, 
 
 void solve_single(SingleState& s) {
   const int N = s.cfg.horizon;
+  s.eval_ok = false;
   if (N < 1 || N > CMPC_MAX_HORIZON) {
     std::fprintf(stderr, "[cmpc] horizon %d out of range\n", N);
     return;
@@ -768,6 +839,7 @@ void solve_single(SingleState& s) {
   s.q_soln.assign(12 * N, 0.0);
   for (int i = 0; i < 12 * N; i++) s.q_soln[i] = forces[i];
   s.has_solved = 1;
+  s.eval_ok = true;
 }
 }  // namespace
 
@@ -854,6 +926,27 @@ extern "C" void update_problem_data(double* p, double* v, double* q, double* w, 
 void update_x_drag(float x_drag) {
   std::lock_guard<std::mutex> lk(g.mu);
   g.x_drag = x_drag;
+}
+
+extern "C" int cmpc_evaluate_last(float* x_pred, double* cert) {
+  std::lock_guard<std::mutex> lk(g.mu);
+  if (!g.has_solved || !g.eval_ok || !g.h) {
+    g_last_error = "cmpc_evaluate_last: no solved update_problem_data* call to evaluate";
+    return -4;
+  }
+  // the record as the solve read it (f_est(3) and its flag written by the device estimator step)
+  // is still in the handle's staging; the forces are q_soln, which get_solution returns
+  const int N = g.h_horizon;
+  if ((int)g.q_soln.size() != 12 * N) {
+    g_last_error = "cmpc_evaluate_last: the last solution is of another horizon";
+    return -4;
+  }
+  std::vector<float> rec(CMPC_REC_WORDS(N)), forces(12 * N);
+  hipError_t e = hipStreamSynchronize(g.h->stream);
+  if (e == hipSuccess) e = hipMemcpy(rec.data(), g.h->d_rec, rec.size() * sizeof(float), hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return fail("D2H", e);
+  for (int i = 0; i < 12 * N; i++) forces[i] = (float)g.q_soln[i];
+  return cmpc_batch_evaluate_host(g.h, rec.data(), forces.data(), 1, x_pred, cert);
 }
 
 extern "C" double get_solution(int index) {

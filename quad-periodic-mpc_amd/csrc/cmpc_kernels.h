@@ -167,6 +167,11 @@ hipError_t launch_rollout(float* d_loco, const float* d_recs, const float* d_for
 // instance (cmpc_condense.hip)
 hipError_t launch_condense(const float* d_recs, int batch, const KParams& P, float* d_H, float* d_g,
                            hipStream_t stream);
+// fp64 prediction, cost and optimality gap of given forces [batch x 12N] (cmpc_evaluate.hip), one
+// wavefront per instance; alpha = the force regularisation (KParams holds 2 alpha in fp32 only).
+// d_xpred / d_cert: either may be NULL
+hipError_t launch_evaluate(const float* d_recs, const float* d_forces, int batch, const KParams& P,
+                           double alpha, float* d_xpred, double* d_cert, hipStream_t stream);
 
 // use_jcqp == 1 / 2: batched JCQP ADMM over the full / reduced condensed QP (cmpc_admm.hip).
 // Instances whose QP has n > 120 variables run on nslabs persistent workgroups with M in

@@ -30,6 +30,10 @@ EST_STOP = 500
 EST_F, EST_T, EST_COUNT, EST_HEAD, EST_FEST3, EST_PARAMS = 0, 400, 800, 801, 802, 804
 EST_WORDS = 816
 
+# words of a certificate row of BatchSolver.evaluate (CMPC_CERT_* of include/cmpc_solver.h)
+CERT_COST, CERT_COST0, CERT_GAP, CERT_VIOL, CERT_SWING, CERT_GRADMAX = range(6)
+CERT_WORDS = 8
+
 STATUS_NAMES = {0: "ok", 1: "max_iter", 2: "infeasible", 3: "not_pd", 4: "bad_input"}
 # locomotion-controller state for batched input assembly (include/cmpc_solver.h CMPC_LOCO_*)
 LOCO_POS, LOCO_ZGT, LOCO_Q, LOCO_RPY, LOCO_VW, LOCO_WW, LOCO_PFOOT = 0, 3, 4, 8, 11, 14, 17

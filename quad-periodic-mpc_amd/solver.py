@@ -20,6 +20,8 @@ import os
 import numpy as np
 
 from .records import CmpcParams, LocoParams, make_params, record_words
+from .records import (CERT_COST, CERT_COST0, CERT_GAP, CERT_VIOL, CERT_SWING, CERT_GRADMAX,  # noqa: F401
+                      CERT_WORDS, MAX_HORIZON)
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CMPC_LIB", os.path.join(PKG, "libcmpc_hip.so"))
@@ -35,6 +37,7 @@ EXPORTED_SYMBOLS = (
     "cmpc_batch_stream",
     "cmpc_last_error", "cmpc_batch_enable_timing", "cmpc_batch_enable_timing_every", "cmpc_batch_read_timing", "cmpc_batch_estimate",
     "cmpc_batch_assemble", "cmpc_batch_rollout", "cmpc_batch_admm", "cmpc_batch_expand",
+    "cmpc_batch_evaluate", "cmpc_batch_evaluate_host", "cmpc_evaluate_last",
     "cmpc_batch_quadprog",   # include/cmpc_quadprog.h
 )
 
@@ -116,6 +119,11 @@ def load_library(path: str = LIB_PATH):
     lib.cmpc_batch_rollout.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                        ctypes.c_int]
+    if hasattr(lib, "cmpc_batch_evaluate"):  # (A/B libraries built before the evaluate unit lack it)
+        lib.cmpc_batch_evaluate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                            ctypes.c_void_p, ctypes.c_void_p]
+        lib.cmpc_batch_evaluate_host.argtypes = [ctypes.c_void_p, _fp, _fp, ctypes.c_int, _fp, _dp]
+        lib.cmpc_evaluate_last.argtypes = [_fp, _dp]
     lib.cmpc_batch_quadprog.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int] + \
         [ctypes.c_void_p] * 7 + [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int]
     _lib = lib
@@ -139,7 +147,9 @@ def _f32(a, n=None):
 
 
 def setup_problem(dt: float, horizon: int, mu: float, f_max: float) -> None:
+    global _setup_horizon
     load_library().setup_problem(dt, horizon, mu, f_max)
+    _setup_horizon = int(horizon)
 
 
 def update_solver_settings(max_iter, rho, sigma, solver_alpha, terminate, use_jcqp) -> None:
@@ -173,6 +183,21 @@ def update_problem_data(p, v, q, w, r, yaw, weights, state_trajectory, alpha, ga
 
 def get_solution(index: int) -> float:
     return load_library().get_solution(int(index))
+
+
+def evaluate_last():
+    """``cmpc_evaluate_last``: the fp64 evaluation of the last ``update_problem_data*`` call's
+    record and solution -> (x_pred [N, 12] float32, cert [CERT_WORDS] float64). Runs on request
+    only; raises before the first solve."""
+    lib = load_library()
+    x_pred = np.zeros(12 * MAX_HORIZON, np.float32)
+    cert = np.zeros(CERT_WORDS, np.float64)
+    _check(lib.cmpc_evaluate_last(x_pred.ctypes.data_as(_fp), cert.ctypes.data_as(_dp)),
+           "cmpc_evaluate_last")
+    return x_pred[:12 * _setup_horizon].reshape(-1, 12).copy(), cert
+
+
+_setup_horizon = 0  # horizon of the last setup_problem (the steps evaluate_last returns)
 
 
 def set_f_ext(values) -> None:
@@ -287,6 +312,45 @@ class BatchSolver:
                                               status.ctypes.data_as(_u8p),
                                               iters.ctypes.data_as(_ip)), "cmpc_batch_solve_host")
         return forces, status, iters
+
+    def evaluate(self, records, forces, x_pred=None, cert=None, batch: int | None = None) -> None:
+        """fp64 prediction, cost and optimality gap of ``forces`` [B, 12N] float32 on device
+        (``cmpc_batch_evaluate``; asynchronous on the handle's stream). ``x_pred`` [B, 12N]
+        float32 and ``cert`` [B, CERT_WORDS] float64 are outputs; either may be None, not both.
+        The forces may come from any solver; a handle that keeps fewer than N output steps
+        (:meth:`set_output_steps`) is refused."""
+        if batch is None:
+            batch = records.shape[0]
+        if batch > self.max_batch:
+            raise CmpcError(f"batch {batch} > max_batch {self.max_batch}")
+        n = 12 * self.horizon
+        if hasattr(records, "shape"):
+            assert records.shape[-1] == self.record_words, "record stride mismatch"
+        if hasattr(forces, "numel"):
+            assert forces.dtype.is_floating_point and forces.element_size() == 4, "forces must be float32"
+            assert forces.numel() >= batch * n
+        if hasattr(x_pred, "numel"):
+            assert x_pred.element_size() == 4 and x_pred.numel() >= batch * n, "x_pred must be float32 [B, 12N]"
+        if hasattr(cert, "numel"):
+            assert cert.element_size() == 8 and cert.dtype.is_floating_point, "cert must be float64"
+            assert cert.numel() >= batch * CERT_WORDS
+        _check(self.lib.cmpc_batch_evaluate(self._h, _ptr(records), _ptr(forces), int(batch),
+                                            _ptr(x_pred), _ptr(cert)), "cmpc_batch_evaluate")
+
+    def evaluate_host(self, records: np.ndarray, forces: np.ndarray):
+        """Host arrays in/out (H2D + kernel + D2H, synchronous) -> (x_pred [B, N, 12] float32,
+        cert [B, CERT_WORDS] float64)."""
+        records = np.ascontiguousarray(records, np.float32)
+        forces = np.ascontiguousarray(forces, np.float32)
+        B = records.shape[0]
+        assert records.shape[1] == self.record_words and forces.size == B * 12 * self.horizon
+        x_pred = np.zeros((B, self.horizon, 12), np.float32)
+        cert = np.zeros((B, CERT_WORDS), np.float64)
+        _check(self.lib.cmpc_batch_evaluate_host(self._h, records.ctypes.data_as(_fp),
+                                                 forces.ctypes.data_as(_fp), B,
+                                                 x_pred.ctypes.data_as(_fp), cert.ctypes.data_as(_dp)),
+               "cmpc_batch_evaluate_host")
+        return x_pred, cert
 
     def condense(self, records, H, g, batch: int | None = None) -> None:
         """Full (no elimination) qH [B,12N,12N] / qg [B,12N] on device — parity hook."""
