@@ -222,6 +222,24 @@ CMPC_EXTERNC void cmpc_batch_destroy(cmpc_batch* h);
  * (may be NULL). Asynchronous on the handle's stream. Returns 0 or a negative error. */
 CMPC_EXTERNC int cmpc_batch_solve(cmpc_batch* h, const float* d_records, int batch,
                                   float* d_forces, uint8_t* d_status, int32_t* d_iters);
+/* The same solve for the instances with an MPC step due this tick, for batches whose
+ * iterationCounters are not in lockstep. d_due: `batch` bytes, the array cmpc_batch_assemble
+ * writes; instance i is due iff d_due[i] != 0 (the test of cmpc_batch_rollout); bytes at index
+ * `batch` and beyond are never read. d_due == NULL is exactly cmpc_batch_solve (the same launch
+ * sequence, not a mask of ones).
+ *   due:     forces, status and iters are bit for bit what cmpc_batch_solve writes for the same
+ *            record, in every size class, launch form and batch size, with the same
+ *            cmpc_batch_set_output_steps stride and cmpc_batch_set_refine setting;
+ *   not due: the record is never read (it may hold anything, NaN words and arbitrary gait bytes
+ *            included), and the instance's rows of d_forces, d_status and d_iters are not
+ *            written: they keep the caller's previous values, so a robot holds its last forces
+ *            until its next MPC step.
+ * Asynchronous on the handle's stream, joined as cmpc_batch_solve is: when the handle's stream
+ * reaches the end of the call every size class has finished. No allocation and no host
+ * synchronisation inside. Argument checks and error returns of cmpc_batch_solve. The timing hooks
+ * below record around it as well; class1_overflow then counts due instances only. New API. */
+CMPC_EXTERNC int cmpc_batch_solve_due(cmpc_batch* h, const float* d_records, const uint8_t* d_due,
+                                      int batch, float* d_forces, uint8_t* d_status, int32_t* d_iters);
 /* Forces kept per instance: the first `steps` horizon steps (12 x steps floats per instance,
  * stride of d_forces / forces of the two solves below and of cmpc_batch_rollout), 0 = every step
  * (12N, the default). A caller that reads only get_solution(0..11) as ConvexMPCLocomotion.cpp:
@@ -326,6 +344,15 @@ CMPC_EXTERNC int cmpc_batch_admm(cmpc_batch* h, const float* d_records, const fl
 CMPC_EXTERNC int cmpc_batch_estimate(cmpc_batch* h, float* d_est, const float* d_logs,
                                      const float* d_fext3, const float* d_time, float sim_time,
                                      float* d_records, float* d_fext6, int batch);
+/* The same step for the due instances only (d_due as for cmpc_batch_solve_due; NULL is exactly
+ * cmpc_batch_estimate): the reference runs its estimator inside solve_mpc, i.e. on MPC ticks. A
+ * due instance gets bit for bit the step of cmpc_batch_estimate; of an instance that is not due
+ * neither the d_est state, nor the record's CMPC_REC_FEST3 / CMPC_REC_FLAGS words, nor the
+ * d_fext6 row is touched. Argument checks and error returns of cmpc_batch_estimate. New API. */
+CMPC_EXTERNC int cmpc_batch_estimate_due(cmpc_batch* h, float* d_est, const float* d_logs,
+                                         const float* d_fext3, const float* d_time, float sim_time,
+                                         float* d_records, float* d_fext6, const uint8_t* d_due,
+                                         int batch);
 /* One control tick of every instance's locomotion controller (batched
  * ConvexMPCLocomotion::run MPC side): updates the state words of d_loco [batch *
  * CMPC_LOCO_WORDS]; where an MPC step is due (iterationCounter % iters_between_mpc == 0 after
@@ -350,7 +377,8 @@ CMPC_EXTERNC int cmpc_batch_rollout(cmpc_batch* h, float* d_loco, const float* d
 /* Measurement hooks: record HIP events on the handle's stream around the next `steps` solves;
  * read back per-solve ms pairs [class 1's launch, the time after it until the wide size classes
  * have joined] and the number of instances the last solve listed for the wide classes
- * (n > 64). Synchronises. */
+ * (n > 64). Synchronises. cmpc_batch_solve_due is recorded the same way (its classify pass
+ * precedes the first event); the count is then of due instances only. */
 CMPC_EXTERNC int cmpc_batch_enable_timing(cmpc_batch* h, int steps);
 /* The same on every `every`-th solve only (the first of each group of `every`), `steps` of them:
  * a timed loop then pays the event packets on a fraction of its solves. */

@@ -336,6 +336,38 @@ extern "C" int cmpc_batch_solve(cmpc_batch* h, const float* d_records, int batch
   return 0;
 }
 
+extern "C" int cmpc_batch_solve_due(cmpc_batch* h, const float* d_records, const uint8_t* d_due, int batch,
+                                    float* d_forces, uint8_t* d_status, int32_t* d_iters) {
+  if (!d_due) return cmpc_batch_solve(h, d_records, batch, d_forces, d_status, d_iters);
+  if (!h || batch < 0 || batch > h->max_batch || (!d_records && batch) || (!d_forces && batch) ||
+      (!d_status && batch)) {
+    g_last_error = "cmpc_batch_solve_due: bad arguments";
+    return -1;
+  }
+  hipEvent_t* ev = nullptr;
+  if (h->ev_steps > 0 && h->ev_next < h->ev_steps && h->ev_solves++ % h->ev_every == 0)
+    ev = &h->ev[3 * h->ev_next++];
+  const hipError_t e = cmpc::launch_solve(d_records, batch, h->kp, d_forces, d_status, d_iters, h->d_work,
+                                          h->max_batch, h->stream, h->ctx, ev, d_due);
+  if (e != hipSuccess) return fail("launch_solve", e);
+  return 0;
+}
+
+extern "C" int cmpc_batch_estimate_due(cmpc_batch* h, float* d_est, const float* d_logs,
+                                       const float* d_fext3, const float* d_time, float sim_time,
+                                       float* d_records, float* d_fext6, const uint8_t* d_due, int batch) {
+  if (!d_due) return cmpc_batch_estimate(h, d_est, d_logs, d_fext3, d_time, sim_time, d_records, d_fext6, batch);
+  if (!h || batch < 0 || batch > h->max_batch || (batch && (!d_est || !d_records)) ||
+      (batch && !d_logs && !d_fext3)) {
+    g_last_error = "cmpc_batch_estimate_due: bad arguments";
+    return -1;
+  }
+  hipError_t e = cmpc::launch_estimate(d_est, d_logs, d_fext3, d_time, sim_time, d_records, h->kp.rec_words,
+                                       d_fext6, h->d_gauss, batch, h->stream, nullptr, d_due);
+  if (e != hipSuccess) return fail("launch_estimate", e);
+  return 0;
+}
+
 extern "C" int cmpc_batch_estimate(cmpc_batch* h, float* d_est, const float* d_logs,
                                    const float* d_fext3, const float* d_time, float sim_time,
                                    float* d_records, float* d_fext6, int batch) {

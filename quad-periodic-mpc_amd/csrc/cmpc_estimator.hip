@@ -248,13 +248,19 @@ __device__ void residual(const float* __restrict__ lg, const float* __restrict__
   f_ext[5] = e11;
 }
 
-__global__ __launch_bounds__(NT) void cmpc_estimate_kernel(
+// One estimator step of instance blockIdx.x. DUE (cmpc_batch_estimate_due): the workgroup of an
+// instance that is not due returns before its first barrier, LDS write or global access other than
+// the due byte. The unmasked kernel below is the DUE = false body under its unchanged signature.
+template <bool DUE>
+__device__ __forceinline__ void estimate_step(
     float* __restrict__ est, const float* __restrict__ logs, const float* __restrict__ fext3,
     const float* __restrict__ times, float sim_time, float* __restrict__ recs, int rec_words,
-    float* __restrict__ fext6, const float* __restrict__ gauss, int batch, float* __restrict__ fest_out) {
+    float* __restrict__ fext6, const float* __restrict__ gauss, int batch, float* __restrict__ fest_out,
+    const uint8_t* __restrict__ due) {
   __shared__ SharedE sh;
   const int inst = blockIdx.x;
   if (inst >= batch) return;
+  if (DUE && due[inst] == 0) return;
   const int tid = threadIdx.x;
   float* st = est + (size_t)inst * CMPC_EST_WORDS;
   float* rec = recs + (size_t)inst * rec_words;
@@ -376,15 +382,35 @@ __global__ __launch_bounds__(NT) void cmpc_estimate_kernel(
   }
 }
 
+__global__ __launch_bounds__(NT) void cmpc_estimate_kernel(
+    float* __restrict__ est, const float* __restrict__ logs, const float* __restrict__ fext3,
+    const float* __restrict__ times, float sim_time, float* __restrict__ recs, int rec_words,
+    float* __restrict__ fext6, const float* __restrict__ gauss, int batch, float* __restrict__ fest_out) {
+  estimate_step<false>(est, logs, fext3, times, sim_time, recs, rec_words, fext6, gauss, batch, fest_out,
+                       nullptr);
+}
+
+__global__ __launch_bounds__(NT) void cmpc_estimate_due_kernel(
+    float* __restrict__ est, const float* __restrict__ logs, const float* __restrict__ fext3,
+    const float* __restrict__ times, float sim_time, float* __restrict__ recs, int rec_words,
+    float* __restrict__ fext6, const float* __restrict__ gauss, int batch, float* __restrict__ fest_out,
+    const uint8_t* __restrict__ due) {
+  estimate_step<true>(est, logs, fext3, times, sim_time, recs, rec_words, fext6, gauss, batch, fest_out, due);
+}
+
 }  // namespace
 
 hipError_t launch_estimate(float* d_est, const float* d_logs, const float* d_fext3,
                            const float* d_time, float sim_time, float* d_records, int rec_words,
                            float* d_fext6, const float* d_gauss, int batch, hipStream_t stream,
-                           float* d_fest_out) {
+                           float* d_fest_out, const uint8_t* d_due) {
   if (batch <= 0) return hipSuccess;
-  hipLaunchKernelGGL(cmpc_estimate_kernel, dim3(batch), dim3(NT), 0, stream, d_est, d_logs, d_fext3,
-                     d_time, sim_time, d_records, rec_words, d_fext6, d_gauss, batch, d_fest_out);
+  if (d_due)
+    hipLaunchKernelGGL(cmpc_estimate_due_kernel, dim3(batch), dim3(NT), 0, stream, d_est, d_logs, d_fext3,
+                       d_time, sim_time, d_records, rec_words, d_fext6, d_gauss, batch, d_fest_out, d_due);
+  else
+    hipLaunchKernelGGL(cmpc_estimate_kernel, dim3(batch), dim3(NT), 0, stream, d_est, d_logs, d_fext3,
+                       d_time, sim_time, d_records, rec_words, d_fext6, d_gauss, batch, d_fest_out);
   return hipGetLastError();
 }
 

@@ -65,7 +65,9 @@ constexpr int kLists = 11;
 constexpr int kHdr = 32;
 constexpr int kDeq = 16;  // cnt[kDeq + list]: dequeue counter of a persistent class's workgroups
 constexpr int kHdrBatch = 31;  // cnt[kHdrBatch]: the batch of the solve that counted into the header
-static_assert(1 + kLists <= kDeq && kDeq + kLists <= kHdrBatch && kHdrBatch < kHdr,
+                               // (a due-masked solve: the number of due instances it counted)
+constexpr int kHdrCall = 30;   // cnt[kHdrCall]: a due-masked solve's whole batch (0: an unmasked solve)
+static_assert(1 + kLists <= kDeq && kDeq + kLists <= kHdrCall && kHdrCall < kHdrBatch && kHdrBatch < kHdr,
               "list lengths, dequeue counters and the batch tag fit the header");
 inline size_t work_ints(int max_batch) { return 2 * kHdr + kLists * (size_t)max_batch; }
 // Side streams and events of one handle: the wider size classes run concurrently with class 1
@@ -90,9 +92,13 @@ struct LaunchCtx {
 };
 // ev (optional): 3 events recorded on `stream`: ev[0] before class 1, ev[1] after it, ev[2]
 // after the wider classes (side streams) have joined.
+// d_due (optional, cmpc_batch_solve_due): batch bytes; only the instances with d_due[i] != 0 are
+// classified, listed and solved, class 1 over its list at every horizon. nullptr: the unmasked
+// launch sequence.
 hipError_t launch_solve(const float* d_recs, int batch, const KParams& P, float* d_forces,
                         uint8_t* d_status, int32_t* d_iters, int* d_work, int max_batch,
-                        hipStream_t stream, LaunchCtx& ctx, hipEvent_t* ev = nullptr);
+                        hipStream_t stream, LaunchCtx& ctx, hipEvent_t* ev = nullptr,
+                        const uint8_t* d_due = nullptr);
 // per-class launchers (cmpc_class1.hip, cmpc_wide_w*.hip)
 hipError_t launch_class1(int nv, const float* d_recs, int batch, const KParams& P, float* d_forces,
                          uint8_t* d_status, int32_t* d_iters, const int* in_list, const int* in_count,
@@ -148,11 +154,12 @@ constexpr int kGaussR7 = 21;   // ceil(3 * 7)
 constexpr int kGaussR27 = 81;  // ceil(3 * 27)
 constexpr int kGaussTaps = 2 * kGaussR7 + 1 + 2 * kGaussR27 + 1;
 // d_fest_out (optional): f_est(3) of instance i also to d_fest_out[i] (the single-instance ABI
-// reads it back with the forces)
+// reads it back with the forces). d_due (optional, cmpc_batch_estimate_due): the workgroup of an
+// instance with d_due[i] == 0 exits before it reads or writes anything else
 hipError_t launch_estimate(float* d_est, const float* d_logs, const float* d_fext3,
                            const float* d_time, float sim_time, float* d_records, int rec_words,
                            float* d_fext6, const float* d_gauss, int batch, hipStream_t stream,
-                           float* d_fest_out = nullptr);
+                           float* d_fest_out = nullptr, const uint8_t* d_due = nullptr);
 // batched input assembly (cmpc_assemble.hip): one control tick per instance
 hipError_t launch_assemble(float* d_loco, const LocoParams& lp, float* d_recs, uint8_t* d_due,
                            int batch, hipStream_t stream);

@@ -7,6 +7,8 @@
 //     streams forked after classify, so they run concurrently with class 1 and with each
 //     other. At N = 10 they are a latency-bound tail (few, long solves); at N = 16..20 the 128-
 //     and 192-column classes carry the batch and run side by side on the two streams.
+//   due form (cmpc_batch_solve_due): the classify pass lists only the due instances and every
+//     class, class 1 included, runs over its list.
 #include <math.h>
 #include <stdlib.h>
 
@@ -19,13 +21,16 @@ namespace {
 // one thread per instance; wave-aggregated appends to the class lists. One-wave workgroups: beside
 // class 1 (whose one-wave workgroups take every wave slot as it frees) a 4-wave workgroup waited
 // for four free slots at once, and the pass took 1.0 ms instead of 0.05
-__global__ __launch_bounds__(64) void cmpc_classify_kernel(const float* __restrict__ recs, int batch,
-                                                           KParams P, int* __restrict__ cnt,
-                                                           int* __restrict__ lists, int max_batch,
-                                                           int c1_max, int* __restrict__ next_hdr,
-                                                           int c1_listed, int tail,
-                                                           int* __restrict__ host_hint,
-                                                           unsigned list_mask, int header_duty) {
+// DUE (cmpc_batch_solve_due): a thread whose instance is not due classifies nothing and reads no
+// record word; cnt[kHdrBatch] counts the due instances and cnt[kHdrCall] holds the whole batch. The
+// unmasked kernel below is the DUE = false body under its unchanged signature.
+template <bool DUE>
+__device__ __forceinline__ void classify_body(const float* __restrict__ recs, const uint8_t* __restrict__ due,
+                                              int batch, const KParams& P, int* __restrict__ cnt,
+                                              int* __restrict__ lists, int max_batch, int c1_max,
+                                              int* __restrict__ next_hdr, int c1_listed, int tail,
+                                              int* __restrict__ host_hint, unsigned list_mask,
+                                              int header_duty) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   const int lane = threadIdx.x & 63;
   if (header_duty && blockIdx.x == 0 && threadIdx.x < kHdr) {
@@ -34,9 +39,15 @@ __global__ __launch_bounds__(64) void cmpc_classify_kernel(const float* __restri
     if (host_hint) host_hint[threadIdx.x] = next_hdr[threadIdx.x];
     next_hdr[threadIdx.x] = 0;
   }
-  if (header_duty && blockIdx.x == 0 && threadIdx.x == 0) cnt[kHdrBatch] = batch;  // this solve's batch: the hint's scale
+  if (!DUE && header_duty && blockIdx.x == 0 && threadIdx.x == 0) cnt[kHdrBatch] = batch;  // this solve's batch: the hint's scale
+  if (DUE && header_duty && blockIdx.x == 0 && threadIdx.x == 0) cnt[kHdrCall] = batch;
   int cls = -1;
-  if (i < batch) {
+  const bool mine = i < batch && (!DUE || due[i] != 0);
+  if (DUE) {  // the hint's scale of a due solve: the instances it solves (the header starts at zero)
+    const unsigned long long nd = __ballot(mine);
+    if (header_duty && lane == 0 && nd) atomicAdd(&cnt[kHdrBatch], __popcll(nd));
+  }
+  if (mine) {
     const uint32_t* g =
         reinterpret_cast<const uint32_t*>(recs + (size_t)i * P.rec_words + CMPC_REC_GAIT(P.N));
     int nfs = 0;
@@ -73,6 +84,27 @@ __global__ __launch_bounds__(64) void cmpc_classify_kernel(const float* __restri
     base = __shfl(base, leader);
     if (cls == c) lists[(size_t)c * max_batch + base + __popcll(m & ((1ull << lane) - 1ull))] = i;
   }
+}
+
+__global__ __launch_bounds__(64) void cmpc_classify_kernel(const float* __restrict__ recs, int batch,
+                                                           KParams P, int* __restrict__ cnt,
+                                                           int* __restrict__ lists, int max_batch,
+                                                           int c1_max, int* __restrict__ next_hdr,
+                                                           int c1_listed, int tail,
+                                                           int* __restrict__ host_hint,
+                                                           unsigned list_mask, int header_duty) {
+  classify_body<false>(recs, nullptr, batch, P, cnt, lists, max_batch, c1_max, next_hdr, c1_listed, tail,
+                       host_hint, list_mask, header_duty);
+}
+
+__global__ __launch_bounds__(64) void cmpc_classify_due_kernel(const float* __restrict__ recs,
+                                                               const uint8_t* __restrict__ due, int batch,
+                                                               KParams P, int* __restrict__ cnt,
+                                                               int* __restrict__ lists, int max_batch,
+                                                               int c1_max, int* __restrict__ next_hdr,
+                                                               int tail, int* __restrict__ host_hint) {
+  classify_body<true>(recs, due, batch, P, cnt, lists, max_batch, c1_max, next_hdr, 1, tail, host_hint,
+                      (1u << kLists) - 1u, 1);
 }
 
 // Launch form of the wide class holding n in [lo, hi] (cmpc_wide.h): one workgroup per list entry
@@ -116,7 +148,13 @@ bool one_per_entry(int lo, int hi, int N, int batch) {
 
 hipError_t launch_solve(const float* d_recs, int batch, const KParams& P, float* d_forces,
                         uint8_t* d_status, int32_t* d_iters, int* d_work, int max_batch,
-                        hipStream_t stream, LaunchCtx& ctx, hipEvent_t* ev) {
+                        hipStream_t stream, LaunchCtx& ctx, hipEvent_t* ev, const uint8_t* d_due) {
+  // The due form (d_due, cmpc_batch_solve_due): the classify pass (its due
+  // instantiation) first on the handle's stream at every horizon, class 1 behind it over list 5
+  // (and list 7 on side 1 where the 60 / 64 split applies), the tail and wide classes over their
+  // lists on the side streams as below. Everything here that does not test `due` is the unmasked
+  // sequence.
+  const bool due = d_due != nullptr;
   int* cnt = d_work + ctx.hdr * kHdr;             // zero: zeroed at create or by the last classify
   int* next_hdr = d_work + (ctx.hdr ^ 1) * kHdr;  // the next solve's, zeroed by this one's classify
   int* list[kLists];
@@ -162,8 +200,8 @@ hipError_t launch_solve(const float* d_recs, int batch, const KParams& P, float*
   // wide classes (hinted grids) launched on their side streams ahead of class 1, so their long
   // solves take SIMD slots before class 1's waves fill the GPU; 2: class 1 over its classify list
   static const int wf_env = diag_knob("CMPC_WIDE_FIRST", 0);
-  const bool wide_first = wf_env > 0 && !c1_listed && n_max > 64;
-  const bool c1_list_mode = c1_listed || (wide_first && wf_env == 2);
+  const bool wide_first = wf_env > 0 && !c1_listed && n_max > 64 && !due;
+  const bool c1_list_mode = c1_listed || (wide_first && wf_env == 2) || due;
   static const int t8_env = diag_knob("CMPC_T8_POS", -1);
   // CMPC_TAIL_SELF=G (A/B, N <= 10): the tail class in its self-classifying form (no classify
   // list) on side 2 ahead of everything, G workgroups (1: one per chunk) over chunks of
@@ -171,7 +209,7 @@ hipError_t launch_solve(const float* d_recs, int batch, const KParams& P, float*
   // waiting for class-1 waves to retire
   static const int tself_env = diag_knob("CMPC_TAIL_SELF", 0);
   static const int tself_chunk = diag_knob("CMPC_TAIL_SELF_CHUNK", 64);
-  const bool tail_self = tself_env > 0 && tail_on && tself_chunk >= 1 && tself_chunk <= 64;
+  const bool tail_self = tself_env > 0 && tail_on && tself_chunk >= 1 && tself_chunk <= 64 && !due;
   const int t8_pos = tail_self ? -1 : (t8_env >= 0) ? t8_env : ((batch >= 131072 && !wide_first) ? 1 : 2);
   // side streams forked and joined by this solve (the third only for the tail class's own chain)
   const int nsides = (tail && (t8_pos == 2 || tail_self)) ? 3 : 2;
@@ -198,6 +236,24 @@ hipError_t launch_solve(const float* d_recs, int batch, const KParams& P, float*
         (e = launch_handoff(ctx.side[2])) != hipSuccess)
       return e;
   }
+  if (due && n_max <= 64) {
+    // the horizons whose unmasked solve needs no classify pass (every n <= 60): the due form lists
+    // the due instances (all in list 5) and class 1 runs over that list; no side stream is used
+    hipLaunchKernelGGL(cmpc_classify_due_kernel, dim3((batch + 63) / 64), dim3(64), 0, stream, d_recs, d_due,
+                       batch, P, cnt, d_work + 2 * kHdr, max_batch, c1_nv, next_hdr, 0, ctx.d_hint);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    ctx.last_hdr = ctx.hdr;
+    if (!CMPC_HDR_MEMSET) ctx.hdr ^= 1;
+    if (ev) (void)hipEventRecord(ev[0], stream);
+    if ((e = launch_class1(c1_nv, d_recs, batch, P, d_forces, d_status, d_iters, list[5], &cnt[6], nullptr,
+                           nullptr, batch, stream)) != hipSuccess)
+      return e;
+    if (ev) {
+      (void)hipEventRecord(ev[1], stream);
+      (void)hipEventRecord(ev[2], stream);
+    }
+    return hipSuccess;
+  }
   bool cls_side_used = false;
   int tail_grid = batch;  // the tail class's grid (hinted below when the classify pass runs)
   int tail_rest = 0;      // workgroups of its looping launch over entries past that grid
@@ -213,7 +269,9 @@ hipError_t launch_solve(const float* d_recs, int batch, const KParams& P, float*
     // Round-4 sweep (profiles/r04_ab/r04_ks, beside vs ahead): 2048 +2.3 %, 4096 (config 2)
     // +3.2 %, 6144 0, 8192 -2 %, 12288 -1.5 %: beside at the smallest batches too, where class 1
     // starting without the classify pass's queue hop ahead of it pays most
-    const bool cls_side = c1_swap ? true : wide_first ? false : (cls_env < 0) ? (batch >= 16384 || batch <= 4096) : (cls_env == 1);
+    // (the due form: on the handle's stream, where class 1, which waits for its list, follows it in
+    // the same queue)
+    const bool cls_side = due ? false : c1_swap ? true : wide_first ? false : (cls_env < 0) ? (batch >= 16384 || batch <= 4096) : (cls_env == 1);
     cls_side_used = cls_side;
     // CMPC_CLS_ON_TAIL=1 (A/B): the classify pass on the tail class's own stream (side 2), so the
     // tail class follows it in the same queue instead of after a cross-queue event (4096
@@ -242,9 +300,13 @@ hipError_t launch_solve(const float* d_recs, int batch, const KParams& P, float*
     if (per_side)
       for (int s = 1; s < 3; s++)
         if ((e = hipStreamWaitEvent(ctx.side[s], ctx.fork, 0)) != hipSuccess) return e;
-    hipLaunchKernelGGL(cmpc_classify_kernel, dim3((batch + 63) / 64), dim3(64), 0, cs,
-                       d_recs, batch, P, cnt, d_work + 2 * kHdr, max_batch, c1_nv, next_hdr, c1_list_mode ? 1 : 0,
-                       tail ? 1 : 0, ctx.d_hint, per_side ? m0 : all_lists, 1);
+    if (due)
+      hipLaunchKernelGGL(cmpc_classify_due_kernel, dim3((batch + 63) / 64), dim3(64), 0, cs, d_recs, d_due,
+                         batch, P, cnt, d_work + 2 * kHdr, max_batch, c1_nv, next_hdr, tail ? 1 : 0, ctx.d_hint);
+    else
+      hipLaunchKernelGGL(cmpc_classify_kernel, dim3((batch + 63) / 64), dim3(64), 0, cs,
+                         d_recs, batch, P, cnt, d_work + 2 * kHdr, max_batch, c1_nv, next_hdr, c1_list_mode ? 1 : 0,
+                         tail ? 1 : 0, ctx.d_hint, per_side ? m0 : all_lists, 1);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (per_side)
       for (int s = 1; s < 3; s++) {
@@ -284,10 +346,17 @@ hipError_t launch_solve(const float* d_recs, int batch, const KParams& P, float*
     const volatile int* hint = (hint_env && ctx.h_hint && batch >= hint_min) ? ctx.h_hint : nullptr;
     const int hint_batch = hint ? hint[kHdrBatch] : 0;
     const bool hinting = hint_batch > 0;
+    // A due solve leaves the number of due instances in cnt[kHdrBatch], so the scaling above stays
+    // a fraction of the solved instances for whichever form comes next, and its whole batch in
+    // cnt[kHdrCall]. The host does not know how many instances are due now, so a due solve scales a
+    // due solve's counts by the whole batches instead (the same due fraction as the hinted solve, as
+    // a staggered loop has tick after tick), and an unmasked solve's counts as if all were due.
+    const int hint_call = (due && hinting) ? hint[kHdrCall] : 0;
+    const double hint_den = hint_call > 0 ? (double)hint_call : (double)hint_batch;
     for (int j = 0; j < kLists; j++) {
       grid_of[j] = batch;
       if (!hinting) continue;
-      const double g = (double)hint[1 + j] * (double)batch / (double)hint_batch * 1.25 + 64.0;
+      const double g = (double)hint[1 + j] * (double)batch / hint_den * 1.25 + 64.0;
       if (g < (double)batch) grid_of[j] = (int)g;
     }
     grid_of[5] = grid_of[7] = batch;  // class-1 lists: their kernel takes one entry per workgroup

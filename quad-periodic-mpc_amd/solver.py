@@ -38,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "cmpc_last_error", "cmpc_batch_enable_timing", "cmpc_batch_enable_timing_every", "cmpc_batch_read_timing", "cmpc_batch_estimate",
     "cmpc_batch_assemble", "cmpc_batch_rollout", "cmpc_batch_admm", "cmpc_batch_expand",
     "cmpc_batch_evaluate", "cmpc_batch_evaluate_host", "cmpc_evaluate_last",
+    "cmpc_batch_solve_due", "cmpc_batch_estimate_due",
     "cmpc_batch_quadprog",   # include/cmpc_quadprog.h
 )
 
@@ -113,6 +114,13 @@ def load_library(path: str = LIB_PATH):
     lib.cmpc_batch_estimate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+    if hasattr(lib, "cmpc_batch_solve_due"):  # (A/B libraries built before the due forms lack them)
+        lib.cmpc_batch_solve_due.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
+                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        lib.cmpc_batch_estimate_due.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
+                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                ctypes.c_int]
     lib.cmpc_batch_assemble.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.POINTER(LocoParams), ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_int]
@@ -287,8 +295,25 @@ class BatchSolver:
         _check(self.lib.cmpc_batch_set_params(self._h, ctypes.byref(params)), "set_params")
         self.params = params
 
-    def solve(self, records, forces, status, iters=None, batch: int | None = None) -> None:
-        """Asynchronous device solve on the handle's stream (torch tensors or raw pointers)."""
+    @staticmethod
+    def _check_due(due, batch: int, what: str) -> None:
+        """``due`` of the masked entry points: a uint8 device tensor of (at least) ``batch`` bytes."""
+        if not hasattr(due, "data_ptr"):
+            raise CmpcError(f"{what}: due must be a torch.uint8 device tensor")
+        import torch
+        if due.dtype != torch.uint8:
+            raise CmpcError(f"{what}: due must be torch.uint8, got {due.dtype}")
+        if not due.is_cuda:
+            raise CmpcError(f"{what}: due must be a device tensor")
+        if not due.is_contiguous() or due.numel() < batch:
+            raise CmpcError(f"{what}: due holds {due.numel()} contiguous bytes, batch is {batch}")
+
+    def solve(self, records, forces, status, iters=None, batch: int | None = None, due=None) -> None:
+        """Asynchronous device solve on the handle's stream (torch tensors or raw pointers).
+        ``due`` (``cmpc_batch_solve_due``): a uint8 device tensor of ``batch`` bytes, the array
+        :meth:`assemble` writes; only the instances with a nonzero byte are solved, the records of
+        the others are not read and their rows of ``forces`` / ``status`` / ``iters`` keep their
+        values. ``None``: every instance (``cmpc_batch_solve``)."""
         if batch is None:
             batch = records.shape[0]
         if batch > self.max_batch:
@@ -296,8 +321,13 @@ class BatchSolver:
         if hasattr(records, "shape"):
             assert records.shape[-1] == self.record_words, "record stride mismatch"
             assert forces.numel() >= batch * self.out_cols and status.numel() >= batch
-        _check(self.lib.cmpc_batch_solve(self._h, _ptr(records), int(batch), _ptr(forces),
-                                         _ptr(status), _ptr(iters)), "cmpc_batch_solve")
+        if due is None:
+            _check(self.lib.cmpc_batch_solve(self._h, _ptr(records), int(batch), _ptr(forces),
+                                             _ptr(status), _ptr(iters)), "cmpc_batch_solve")
+            return
+        self._check_due(due, int(batch), "solve")
+        _check(self.lib.cmpc_batch_solve_due(self._h, _ptr(records), _ptr(due), int(batch), _ptr(forces),
+                                             _ptr(status), _ptr(iters)), "cmpc_batch_solve_due")
 
     def solve_host(self, records: np.ndarray):
         """Host arrays in/out (H2D + solve + D2H, synchronous) -> (forces, status, iters)."""
@@ -371,17 +401,26 @@ class BatchSolver:
                "cmpc_batch_admm")
 
     def estimate(self, est_state, records, *, logs=None, fext3=None, times=None,
-                 sim_time: float = 0.0, fext6=None, batch: int | None = None) -> None:
+                 sim_time: float = 0.0, fext6=None, batch: int | None = None, due=None) -> None:
         """Config-5 estimator step on device (``cmpc_batch_estimate``): updates ``est_state``
         [B, EST_WORDS] and writes f_est(3) / the use-f_est flag into ``records``. Pass either
-        ``logs`` [B, LOG_WORDS] (residual computed on device) or ``fext3`` [B]."""
+        ``logs`` [B, LOG_WORDS] (residual computed on device) or ``fext3`` [B]. ``due``
+        (``cmpc_batch_estimate_due``): as for :meth:`solve`; the state, record words and ``fext6``
+        row of an instance that is not due are left alone."""
         if batch is None:
             batch = records.shape[0]
         if logs is None and fext3 is None:
             raise CmpcError("estimate needs logs or fext3")
-        _check(self.lib.cmpc_batch_estimate(self._h, _ptr(est_state), _ptr(logs), _ptr(fext3),
-                                            _ptr(times), float(sim_time), _ptr(records),
-                                            _ptr(fext6), int(batch)), "cmpc_batch_estimate")
+        if due is None:
+            _check(self.lib.cmpc_batch_estimate(self._h, _ptr(est_state), _ptr(logs), _ptr(fext3),
+                                                _ptr(times), float(sim_time), _ptr(records),
+                                                _ptr(fext6), int(batch)), "cmpc_batch_estimate")
+            return
+        self._check_due(due, int(batch), "estimate")
+        _check(self.lib.cmpc_batch_estimate_due(self._h, _ptr(est_state), _ptr(logs), _ptr(fext3),
+                                                _ptr(times), float(sim_time), _ptr(records),
+                                                _ptr(fext6), _ptr(due), int(batch)),
+               "cmpc_batch_estimate_due")
 
     def assemble(self, loco, loco_params: LocoParams, records, due, batch: int | None = None) -> None:
         """One control tick of every instance's locomotion controller on device
