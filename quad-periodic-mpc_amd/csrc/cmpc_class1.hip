@@ -316,34 +316,19 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
   CondGeo cg;
   make_cond_geo<true>(srec, md, cg);
   lsync();
-  if (v < N) {
-    float e[13];
-    state_error(srec, md, v, srec + CMPC_REC_HDR + 12 * v, e);
-#pragma unroll
-    for (int j = 0; j < 13; j++) sh.P[OFF_E + 16 * v + j] = e[j];
-  }
-  lsync();
   float wts[13];
 #pragma unroll
   for (int j = 0; j < 12; j++) wts[j] = P.wts[j];
   wts[12] = 0.f;
-  // gradient recursion ze_i = S e_i + Adt' ze_{i+1} (uniform: every lane computes it, lane j
-  // stores component j)
-  {
-    float ze[13];
+  if (v < N) {  // the weighted state error we_v = S e_v of step v
+    float e[13];
+    state_error(srec, md, v, srec + CMPC_REC_HDR + 12 * v, e);
 #pragma unroll
-    for (int j = 0; j < 13; j++) ze[j] = 0.f;
-    for (int i = N - 1; i >= 0; i--) {
-      float e[13];
-#pragma unroll
-      for (int j = 0; j < 13; j++) e[j] = sh.P[OFF_E + 16 * i + j];
-      recur(md, wts, e, ze);
-      float mine = 0.f;
-#pragma unroll
-      for (int j = 0; j < 13; j++) mine = (v == j) ? ze[j] : mine;
-      if (v < 13) sh.P[OFF_ZE + 16 * i + v] = mine;
-    }
+    for (int j = 0; j < 13; j++) sh.P[OFF_E + 16 * v + j] = wts[j] * e[j];
   }
+  lsync();
+  // the gradient's suffix moments (cmpc_common.h): M0 over E in place, M1 / M2 in ZE
+  moment_recur(&sh.P[OFF_E], &sh.P[OFF_ZE], N, v);
   lsync();
   C1_MARK(0);
 
@@ -358,13 +343,10 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
     for (int j = 0; j < 13; j++) b[j] = real ? sh.u.BdtT[cv][j] : 0.f;
     n1_mul(md, b, u1);
     n1_mul(md, u1, u2);
-    {
-      float zk[13];
-#pragma unroll
-      for (int j = 0; j < 13; j++) zk[j] = sh.P[OFF_ZE + 16 * kv + j];
-      gv = real ? 2.f * dot13(b, zk) : 0.f;  // qg = 2 B_qp' S (A_qp x0 + Q_qp f - X_d)
-    }
-    lsync();  // every ZE read is issued before P is overwritten
+    // qg = 2 B_qp' S (A_qp x0 + Q_qp f - X_d)
+    gv = grad_from_moments(b, u1, u2, &sh.P[OFF_E + 16 * kv], &sh.P[OFF_ZE + 16 * kv]);
+    gv = real ? gv : 0.f;
+    lsync();  // every moment read is issued before P is overwritten
     const int myrow = G::tri(v);
     float z[13];
 #pragma unroll

@@ -283,6 +283,53 @@ __device__ __forceinline__ float dot13(const float* a, const float* b) {
   return s;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Gradient from suffix moments. With we_i = w .* e_i and b a column of Bdt entering at step k,
+//   g = 2 b' ze_k,  ze_k = sum_{i>=k} (Adt')^{i-k} we_i,  Adt^m = I + m N1 + m(m-1)/2 N1^2,  so
+//   g = 2 (b . M0_k + u1 . M1_k + u2 . M2_k),  u1 = N1 b, u2 = N1 u1,
+//   M0_k = sum_{i>=k} we_i,  M1_k = sum_{i>=k} (i-k) we_i,  M2_k = sum_{i>=k} C(i-k, 2) we_i.
+// The moments follow by three additions per step and component, going down from k = N-1; nobody
+// runs the 13 x 13 recursion ze_i = we_i + Adt' ze_{i+1}. u1 is nonzero in rows 0..5 and 11 only,
+// u2 in row 5 only (n1_mul, col_power).
+// LDS layout, 16 words per step in each of two arrays: M0_k replaces we_k in place (E), M1_k sits
+// in words 0..12 of the second array (M) and M2_k's row 5 in its word 13.
+// Used by class 1, the wide classes and the parity hook; the tail class (cmpc_tail.hip) keeps the
+// recursion with recur / dot13: one of its kernels spills more with the moments.
+// ---------------------------------------------------------------------------------------------
+constexpr int kMomM2 = 13;  // word of M2_k[5] in step k's 16 words of M
+
+// lane j < 13 owns component j: one LDS read (the next step's, issued ahead of this step's stores)
+// and three adds per step. we_k's row 12 is zero (wts[12] = 0), and so are the moments'.
+__device__ __forceinline__ void moment_recur(float* E, float* M, int N, int lane) {
+  if (lane < 13) {
+    float m0 = 0.f, m1 = 0.f, m2 = 0.f;
+    float we = E[16 * (N - 1) + lane];
+    for (int k = N - 1; k >= 0; k--) {
+      const float nx = (k > 0) ? E[16 * (k - 1) + lane] : 0.f;
+      m2 += m1;
+      m1 += m0;
+      m0 += we;
+      E[16 * k + lane] = m0;
+      M[16 * k + lane] = m1;
+      if (lane == 5) M[16 * k + kMomM2] = m2;
+      we = nx;
+    }
+  }
+}
+
+// g = 2 (b . M0 + u1 . M1 + u2 . M2) from step k's moment words (E0 = E + 16 k, Mk = M + 16 k),
+// the structural zeros of u1 and u2 written out: 13 + 7 + 1 FMAs
+__device__ __forceinline__ float grad_from_moments(const float* b, const float* u1, const float* u2,
+                                                   const float* E0, const float* Mk) {
+  float s = u2[5] * Mk[kMomM2];
+  s = fmaf(u1[11], Mk[11], s);
+#pragma unroll
+  for (int j = 5; j >= 0; j--) s = fmaf(u1[j], Mk[j], s);
+#pragma unroll
+  for (int j = 0; j < 13; j++) s = fmaf(b[j], E0[j], s);
+  return 2.f * s;
+}
+
 // stance mask of horizon step i (bit f: foot f in stance) from the two stance ballots over the
 // foot-steps 4 i + f (m0: foot-steps 0..63, m1: 64..127); uniform
 __device__ __forceinline__ unsigned step_mask(unsigned long long m0, unsigned long long m1, int i) {

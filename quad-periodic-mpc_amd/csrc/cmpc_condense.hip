@@ -31,32 +31,19 @@ __device__ void condense_one(const float* __restrict__ rec, const KParams& P, Sh
   CondGeo cg;
   make_cond_geo<true>(rec, md, cg);
   __syncthreads();
-  if (tid < N) {
-    float e[13];
-    state_error(rec, md, tid, &sh.traj[12 * tid], e);
-#pragma unroll
-    for (int j = 0; j < 13; j++) sh.E[tid][j] = e[j];
-  }
-  __syncthreads();
   float wts[13];
 #pragma unroll
   for (int j = 0; j < 12; j++) wts[j] = P.wts[j];
   wts[12] = 0.f;
-  if (tid < 64) {
-    float ze[13];
+  if (tid < N) {  // the weighted state error we_tid = S e_tid of step tid
+    float e[13];
+    state_error(rec, md, tid, &sh.traj[12 * tid], e);
 #pragma unroll
-    for (int j = 0; j < 13; j++) ze[j] = 0.f;
-    for (int i = N - 1; i >= 0; i--) {
-      float e[13];
-#pragma unroll
-      for (int j = 0; j < 13; j++) e[j] = sh.E[i][j];
-      recur(md, wts, e, ze);
-      if ((tid & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < 13; j++) sh.ZE[i][j] = ze[j];
-      }
-    }
+    for (int j = 0; j < 13; j++) sh.E[tid][j] = wts[j] * e[j];
   }
+  __syncthreads();
+  // the gradient's suffix moments, as in the solvers: M0 over E in place, M1 / M2 in ZE
+  moment_recur(&sh.E[0][0], &sh.ZE[0][0], N, tid);
   __syncthreads();
   // variable v = 12 k + c (every foot-step kept): row v by the backward recursion of its column
   for (int v = tid; v < n; v += NTG) {
@@ -66,12 +53,8 @@ __device__ void condense_one(const float* __restrict__ rec, const KParams& P, Sh
     for (int j = 0; j < 13; j++) b[j] = sh.BdtT[cv][j];
     n1_mul(md, b, u1);
     n1_mul(md, u1, u2);
-    {
-      float zk[13];
-#pragma unroll
-      for (int j = 0; j < 13; j++) zk[j] = sh.ZE[kv][j];
-      g[v] = 2.f * dot13(b, zk);  // qg = 2 B_qp' S (A_qp x0 + Q_qp f - X_d)
-    }
+    // qg = 2 B_qp' S (A_qp x0 + Q_qp f - X_d)
+    g[v] = grad_from_moments(b, u1, u2, sh.E[kv], sh.ZE[kv]);
     float z[13];
 #pragma unroll
     for (int j = 0; j < 13; j++) z[j] = 0.f;

@@ -712,33 +712,20 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
   make_model(srec, P.dt, md);
   make_bdt<G::NT>(srec, md, t, sh.BdtT());
   wbar();
-  if (t < N) {
-    float e[13];
-    state_error(srec, md, t, srec + CMPC_REC_HDR + 12 * t, e);
-#pragma unroll
-    for (int j = 0; j < 13; j++) sh.P[W_OFF_E + 16 * t + j] = e[j];
-  }
-  wbar();
   float wts[13];
 #pragma unroll
   for (int j = 0; j < 12; j++) wts[j] = P.wts[j];
   wts[12] = 0.f;
-  // gradient recursion ze_i = S e_i + Adt' ze_{i+1} (uniform; thread j < 13 stores component j)
-  {
-    float ze[13];
+  if (t < N) {  // the weighted state error we_t = S e_t of step t
+    float e[13];
+    state_error(srec, md, t, srec + CMPC_REC_HDR + 12 * t, e);
 #pragma unroll
-    for (int j = 0; j < 13; j++) ze[j] = 0.f;
-    for (int i = N - 1; i >= 0; i--) {
-      float e[13];
-#pragma unroll
-      for (int j = 0; j < 13; j++) e[j] = sh.P[W_OFF_E + 16 * i + j];
-      recur(md, wts, e, ze);
-      float mine = 0.f;
-#pragma unroll
-      for (int j = 0; j < 13; j++) mine = (t == j) ? ze[j] : mine;
-      if (t < 13) sh.P[W_OFF_ZE + 16 * i + t] = mine;
-    }
+    for (int j = 0; j < 13; j++) sh.P[W_OFF_E + 16 * t + j] = wts[j] * e[j];
   }
+  wbar();
+  // the gradient's suffix moments (cmpc_common.h; thread j < 13 owns component j): M0 over E in
+  // place, M1 / M2 in ZE
+  moment_recur(&sh.P[W_OFF_E], &sh.P[W_OFF_ZE], N, tid_opq());
   wbar();
 
   // ---- condensation: row r's lanes build H[r][w], w >= r (half h takes every other w of a
@@ -754,13 +741,10 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
     for (int j = 0; j < 13; j++) b[j] = real ? sh.BdtT()[cv][j] : 0.f;
     n1_mul(md, b, u1);
     n1_mul(md, u1, u2);
-    {
-      float zk[13];
-#pragma unroll
-      for (int j = 0; j < 13; j++) zk[j] = sh.P[W_OFF_ZE + 16 * kv + j];
-      gv = real ? 2.f * dot13(b, zk) : 0.f;  // qg = 2 B_qp' S (A_qp x0 + Q_qp f - X_d)
-    }
-    wbar();  // every ZE read is done before P is overwritten
+    // qg = 2 B_qp' S (A_qp x0 + Q_qp f - X_d)
+    gv = grad_from_moments(b, u1, u2, &sh.P[W_OFF_E + 16 * kv], &sh.P[W_OFF_ZE + 16 * kv]);
+    gv = real ? gv : 0.f;
+    wbar();  // every moment read is done before P is overwritten
     const int myrow = G::tri(rr);
     float z[13];
 #pragma unroll
@@ -773,8 +757,9 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
       const float k = (float)(i - kv);
       const float k2 = 0.5f * k * (k - 1.f);
       float gk[13];
+      col_power(b, u1, u2, k, k2, gk);
 #pragma unroll
-      for (int j = 0; j < 13; j++) gk[j] = act ? fmaf(k2, u2[j], fmaf(k, u1[j], b[j])) : 0.f;
+      for (int j = 0; j < 13; j++) gk[j] = act ? gk[j] : 0.f;
       recur(md, wts, gk, z);
       const int wb = __builtin_amdgcn_readfirstlane(sh.blkbase[i]);
       const int we = __builtin_amdgcn_readfirstlane(sh.blkbase[i + 1]);
