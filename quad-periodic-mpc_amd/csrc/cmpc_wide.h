@@ -295,7 +295,8 @@ __device__ __forceinline__ int rli_pos(const int (&a)[RQ], int i) {
 //   B  thread (k, j), j < 12: d_k,j (w = B_c u_k from t, s);
 //   C  wave 0, lane j < 12 owns component j: the two recursions, the cross terms by v_readlane;
 //   D  thread (k, i), i < 6: y_k (i < 3) and nu_k[9 + i - 3] / m;
-//   E  row r: its gradient entry, then u = J2' r (the columns of J summed over the rows, by DPP
+//   E  row r: its gradient entry (0 for an axis the foot-step's own active rows pin: its
+//      multiplier, which J2' annihilates exactly), then u = J2' r (the columns of J summed over the rows, by DPP
 //      within a wave and over the waves in order through the LDS: deterministic) and x -= J2 u.
 // The reference's own fp32 pipeline (dense-S GEMMs) is up to ~1e-4 from its QP's exact optimum at
 // N >= 16; after this step the solution lands within ~1e-6 of it.
@@ -584,6 +585,21 @@ __device__ __forceinline__ void wide_refine(const float* __restrict__ rec_in, co
       // (y x r_b)_a = y_a1 r_a2 - y_a2 r_a1
       const double cr = yk[a1] * (double)rec[CMPC_REC_R + 4 * a2 + b] - yk[a2] * (double)rec[CMPC_REC_R + 4 * a1 + b];
       rr = (float)(2.0 * (cr + yk[3 + a]) + (double)sopq(P.alpha2) * (double)xv);
+      // A unit vector the foot-step's own working-set rows span (e_z: fz = 0, fz = ub or two
+      // opposite faces; with it e_x / e_y from one face of that pair) is a combination of rows of
+      // C_W, so J2' annihilates it and the entry does not enter u = J2' r. In fp32 J2's row of such
+      // a variable is ~1e-7, not 0, and the entry is the row's multiplier, orders of magnitude
+      // above the face's residual gradient (f_max = 30: 40-58 rows at fz = ub, entries of 0.4
+      // against 1e-4): it came back through (Z' H Z)^-1 <= 1 / alpha2 as ~5e-4 N. Dropped here,
+      // exactly. (One face alone, with fz free, pins no axis: its entries stay.)
+      unsigned int f4;
+      unsigned short f2;
+      __builtin_memcpy(&f4, &sh.cflag[6 * (r / 3)], 4);
+      __builtin_memcpy(&f2, &sh.cflag[6 * (r / 3) + 4], 2);
+      const bool cx = f4 & 0xffffu, cy = f4 & 0xffff0000u;
+      const bool ez = f2 || (f4 & 0xffu && f4 & 0xff00u) || (f4 & 0xff0000u && f4 & 0xff000000u);
+      const int ax = r - 3 * (r / 3);
+      if (ez && (ax == 2 || (ax == 0 ? cx : cy))) rr = 0.f;
     }
   }
   float pa[NC], pb[NC];

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import evaluate_ref as er
+import param_sets
 from conftest import golden_params, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -23,6 +24,10 @@ BATCHES = [1, 3, 130]
 # N = 1: the recursions end at once; 2; 10 from the edge set (all-swing, one foot, all-stance,
 # first-step-only, x_drag = +-0.5); 11; 20: 240 columns, several per lane
 CASES = ["n1", "n2", "n10_edge", "n11", "n20_mixed", "n20_standing"]
+# "<case>@<set>": the same records and forces under a non-default parameter set of
+# tests/param_sets.py (twelve distinct non-zero weights; mu, f_max, alpha and dt all moved), so a
+# wrong weight index or coefficient in the kernel's closed forms shows; the bars are the same
+CASES += [f"{c}@{s}" for s in ("W1", "all") for c in ("n2", "n10_edge", "n20_mixed")]
 
 
 @pytest.fixture(scope="module")
@@ -68,9 +73,12 @@ def pool(cm, orc, case):
     if case in _POOLS:
         return _POOLS[case]
     rng = np.random.default_rng(20240 + len(case))
+    full_name = case
+    case, _, set_name = case.partition("@")
+    over = param_sets.SETS[set_name or "default"]
     if case.startswith("n") and case[1:].isdigit():
         N = int(case[1:])
-        prm = cm.make_params(N)
+        prm = cm.make_params(N, **over)
         base = cm.make_instances(4, N, seed=811 + N, random_contact_frac=1.0)
         recs, forces = [], []
         for r in base:
@@ -81,6 +89,8 @@ def pool(cm, orc, case):
         g = load_golden(case)
         prm = golden_params(cm, g)
         N = prm.horizon
+        if set_name:
+            prm = cm.make_params(N, **over)
         k = min(6, len(g["records"]))
         recs = [r for r in g["records"][:k]]
         forces = [q.astype(np.float32) for q in g["q_ref"][:k]]
@@ -97,8 +107,8 @@ def pool(cm, orc, case):
                 forces.append(_random_forces(cm, prm, r, rng, feasible))
     recs, forces = np.array(recs, np.float32), np.array(forces, np.float32)
     ref = [er.evaluate(orc, r, prm, u) for r, u in zip(recs, forces)]
-    _POOLS[case] = (prm, recs, forces, np.array([x for x, _ in ref]), np.array([c for _, c in ref]))
-    return _POOLS[case]
+    _POOLS[full_name] = (prm, recs, forces, np.array([x for x, _ in ref]), np.array([c for _, c in ref]))
+    return _POOLS[full_name]
 
 
 def device_evaluate(solver_mod, prm, recs, forces, max_batch=None):
@@ -141,7 +151,7 @@ def test_parity_with_reference(cm, orc, solver_mod, case, B):
     assert (c[:, 6:] == 0).all()
     for name, v in ratios.items():
         assert v.max() <= 1.0, (case, B, name, int(v.argmax()), float(v.max()))
-    if case == "n10_edge":
+    if case.partition("@")[0] == "n10_edge":
         # the all-swing instance (its golden forces are 0): gap = viol = 0, cost = cost0 exactly
         allswing = [i for i in range(B) if not _stance(cm, prm, recs[idx][i]).any() and not forces[idx][i].any()]
         assert B < 6 or allswing
