@@ -34,6 +34,10 @@ CMPC_EXTERNC int cmpc_multi_create(cmpc_multi** out, const cmpc_params* prm, int
                                    const int* devices, int max_batch, float root_share,
                                    int out_steps, int flags);
 CMPC_EXTERNC void cmpc_multi_destroy(cmpc_multi* m);
+/* The robot model (cmpc_model, include/cmpc_solver.h) of every GPU's handle, the peers' included:
+ * cmpc_batch_set_model forwarded (NULL: the default). Applies to the solves made after it; a bad
+ * value returns cmpc_batch_set_model's error and changes no handle. */
+CMPC_EXTERNC int cmpc_multi_set_model(cmpc_multi* m, const cmpc_model* model);
 /* d_records [batch * cmpc_record_words(N)] on the root device; d_forces [batch * out_cols] and
  * d_status [batch] on the root device, in instance order. Asynchronous on root_stream
  * (hipStream_t; NULL = the legacy default stream of the root device): the inputs are read after

@@ -168,6 +168,21 @@ typedef struct cmpc_params {
   int   max_iter;     /* active-set iteration cap (reference: nWSR = 100)                       */
 } cmpc_params;
 
+/* The robot: the single rigid body of the prediction model. The reference hard-codes the A1's
+ * m = 12, I_body = diag(.07, .26, .242) (RobotState.h:25-26), which is the default here; another
+ * robot, a payload or a randomised mass is set per handle (cmpc_batch_set_model) or for the
+ * single-instance surface (cmpc_set_model). The fields are double: the fp32 kernels use (float)
+ * of each field, the fp64 paths (the refinement of the wide classes, cmpc_batch_evaluate) the
+ * doubles themselves, so the default model gives bit for bit what the literals gave.
+ * Not part of the model: gravity (the reference's -9.8 in x0[12] and -9.81 in the config-5
+ * residual both stay), off-diagonal body inertia (principal moments only), and a per-instance
+ * model array (the handle's model is batch-shared, as cmpc_params is). */
+typedef struct cmpc_model {
+  double mass;        /* kg, > 0 */
+  double inertia[3];  /* principal body-frame moments Ixx, Iyy, Izz (kg m^2), each > 0;
+                         I_world = R diag(.) R' */
+} cmpc_model;
+
 typedef struct cmpc_batch cmpc_batch;
 
 /* ------------------------------------------------------------------------------------------ */
@@ -217,6 +232,14 @@ CMPC_EXTERNC int cmpc_batch_create(cmpc_batch** out, const cmpc_params* prm, int
                                    void* hip_stream);
 CMPC_EXTERNC int cmpc_batch_set_params(cmpc_batch* h, const cmpc_params* prm);
 CMPC_EXTERNC void cmpc_batch_destroy(cmpc_batch* h);
+/* The handle's robot model (cmpc_model above); m == NULL sets the default. Handle state of its
+ * own: it survives cmpc_batch_set_params, in either order of the two calls, and applies to every
+ * call made after it (solve, solve_due, condense, evaluate, rollout, and the residual of
+ * cmpc_batch_estimate when d_logs is given; cmpc_batch_admm follows through the H and g it is
+ * given). No allocation and no synchronisation. A non-finite or non-positive field returns -2
+ * (the bad-value error of cmpc_batch_set_params) and leaves the handle unchanged. New API. */
+CMPC_EXTERNC int cmpc_batch_set_model(cmpc_batch* h, const cmpc_model* m);
+CMPC_EXTERNC int cmpc_batch_get_model(const cmpc_batch* h, cmpc_model* out);
 /* Device-resident solve: d_records [batch * cmpc_record_words(N)] fp32, d_forces
  * [batch * 12N] fp32 (step-major, leg*3+axis), d_status [batch] uint8, d_iters [batch] int32
  * (may be NULL). Asynchronous on the handle's stream. Returns 0 or a negative error. */
@@ -302,6 +325,11 @@ CMPC_EXTERNC int cmpc_batch_evaluate_host(cmpc_batch* h, const float* records, c
  * Runs on request only, so the reference protocol's latency is untouched. Returns a negative
  * error before the first solve. New API. */
 CMPC_EXTERNC int cmpc_evaluate_last(float* x_pred, double* cert);
+/* Single-instance surface: the robot model from the next update_problem_data* call on, as
+ * update_solver_settings sets its settings (m == NULL: the default; -2 and no change for a
+ * non-finite or non-positive field). cmpc_evaluate_last evaluates under the model of the solve it
+ * evaluates. New API. */
+CMPC_EXTERNC int cmpc_set_model(const cmpc_model* m);
 /* Parity hook for the condensation rows (SolverMPC.cpp:96-146, 806-814): full 12N x 12N qH
  * (row-major) and qg per instance, all variables kept (no swing elimination). */
 CMPC_EXTERNC int cmpc_batch_condense(cmpc_batch* h, const float* d_records, int batch,

@@ -22,7 +22,7 @@ SOURCES = ["cmpc_tail.hip", "cmpc_wide_w256.hip", "cmpc_wide_w192.hip", "cmpc_cl
            "cmpc_wide_w120.hip", "cmpc_wide_w128.hip", "cmpc_wide_w144.hip", "cmpc_wide_w80p.hip",
            "cmpc_wide_w96p.hip", "cmpc_wide_w120p.hip", "cmpc_wide_w128p.hip", "cmpc_wide_w80r.hip",
            "cmpc_wide_w96r.hip", "cmpc_wide_w120r.hip", "cmpc_wide_w80pr.hip", "cmpc_wide_w96pr.hip",
-           "cmpc_wide_w120pr.hip", "cmpc_condense.hip", "cmpc_launch.hip", "cmpc_estimator.hip", "cmpc_assemble.hip",
+           "cmpc_wide_w120pr.hip", "cmpc_wide_w96prd.hip", "cmpc_wide_w120prd.hip", "cmpc_wide_w96rd.hip", "cmpc_wide_w120rd.hip", "cmpc_condense.hip", "cmpc_launch.hip", "cmpc_estimator.hip", "cmpc_assemble.hip",
            "cmpc_admm.hip", "cmpc_quadprog.hip", "cmpc_evaluate.hip", "cmpc_abi.cpp"]
 ARCH = os.environ.get("CMPC_OFFLOAD_ARCH", "gfx950")
 # -fno-slp-vectorize: the SLP pass packs adjacent row updates into v_pk_fma_f32, which ties
@@ -112,6 +112,14 @@ def build_multi(lib: str = LIB) -> str:
         os.replace(MULTI_LIB + ".tmp", MULTI_LIB)
     exe = os.path.join(PKG, "cmpc_multi_test")
     tsrc = os.path.join(CSRC, "tools", "cmpc_multi_test.cpp")
+    if _stale(exe, [tsrc, MULTI_LIB] + hdrs):
+        subprocess.run([hipcc, "-x", "hip", "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-o", exe + ".tmp",
+                        tsrc, f"-L{PKG}", "-lcmpc_multi", "-lcmpc_hip", "-Wl,-rpath,$ORIGIN",
+                        f"-Wl,-rpath,{PKG}"], check=True)
+        os.replace(exe + ".tmp", exe)
+    # the same kind of caller for cmpc_multi_set_model
+    exe = os.path.join(PKG, "cmpc_multi_model_test")
+    tsrc = os.path.join(CSRC, "tools", "cmpc_multi_model_test.cpp")
     if _stale(exe, [tsrc, MULTI_LIB] + hdrs):
         subprocess.run([hipcc, "-x", "hip", "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-o", exe + ".tmp",
                         tsrc, f"-L{PKG}", "-lcmpc_multi", "-lcmpc_hip", "-Wl,-rpath,$ORIGIN",

@@ -32,6 +32,7 @@ int fail(const char* what, hipError_t e) {
 
 struct cmpc_batch {
   cmpc_params prm;
+  cmpc_model model = {12.0, {0.07, 0.26, 0.242}};  // cmpc_batch_set_model; kept across set_params
   cmpc::KParams kp;
   int out_steps = 0;             // cmpc_batch_set_output_steps (0: every step)
   int refine = 1;                // cmpc_batch_set_refine (1: from N = 11, 0: off)
@@ -124,8 +125,39 @@ void release_sides(const std::array<hipStream_t, cmpc::kSideStreams>& s) {
 }
 }  // namespace
 
-static cmpc::KParams make_kparams(const cmpc_params& p) {
+// The default robot: m = 12, I_body = diag(.07, .26, .242) (RobotState.h:25-26)
+static const cmpc_model kDefaultModel = {12.0, {0.07, 0.26, 0.242}};
+
+// The kernels' form of the model, every derived value formed here once. The fp32 kernels get
+// (float) of each field and 1.f / (float) mass, the fp64 paths the reciprocals of the doubles:
+// for the default these are the values the literals .07f, 1.f / 12.0f, 1.0 / 0.07 and 1.0 / 12.0
+// had, so the default gives the same bits as before the model was a parameter.
+static cmpc::KModel make_kmodel(const cmpc_model& m) {
+  cmpc::KModel k{};
+  for (int i = 0; i < 3; i++) {
+    k.ib[i] = (float)m.inertia[i];
+    k.iinv64[i] = 1.0 / m.inertia[i];
+  }
+  k.im = 1.f / (float)m.mass;
+  k.im64 = 1.0 / m.mass;
+  return k;
+}
+
+static bool model_ok(const cmpc_model& m) {
+  // finite and positive, in double and after the fp32 kernels' cast
+  auto ok = [](double v) { return std::isfinite(v) && v > 0.0 && std::isfinite((float)v) && (float)v > 0.f; };
+  if (!(ok(m.mass) && ok(m.inertia[0]) && ok(m.inertia[1]) && ok(m.inertia[2]))) return false;
+  // and every value derived from them (a denormal mass or inertia has an infinite reciprocal)
+  const cmpc::KModel k = make_kmodel(m);
+  bool fin = std::isfinite(k.im) && k.im > 0.f && std::isfinite(k.im64) && k.im64 > 0.0;
+  for (int i = 0; i < 3; i++) fin = fin && std::isfinite(k.iinv64[i]) && k.iinv64[i] > 0.0;
+  return fin;
+}
+
+static cmpc::KParams make_kparams(const cmpc_params& p, const cmpc_model& m) {
   cmpc::KParams k{};
+  k.mdl = make_kmodel(m);
+  k.mdl_default = std::memcmp(&m, &kDefaultModel, sizeof m) == 0;
   k.dt = p.dt;
   k.mu_inv = 1.f / p.mu;  // fpt mu = 1.f / setup->mu (SolverMPC.cpp:657)
   k.f_max = p.f_max;
@@ -191,10 +223,29 @@ extern "C" int cmpc_batch_set_params(cmpc_batch* h, const cmpc_params* prm) {
     return -2;
   }
   h->prm = *prm;
-  h->kp = make_kparams(*prm);
+  h->kp = make_kparams(*prm, h->model);
   if (h->out_steps > 0 && h->out_steps < prm->horizon) h->kp.out_cols = 12 * h->out_steps;
   if (!h->refine) h->kp.refine = 0;
   return ensure_admm_slabs(h);
+}
+
+extern "C" int cmpc_batch_set_model(cmpc_batch* h, const cmpc_model* m) {
+  if (!h) return -1;
+  const cmpc_model nm = m ? *m : kDefaultModel;
+  if (!model_ok(nm)) {
+    g_last_error = "cmpc_batch_set_model: mass and inertia must be finite and positive";
+    return -2;
+  }
+  h->model = nm;
+  h->kp.mdl = make_kmodel(nm);
+  h->kp.mdl_default = std::memcmp(&nm, &kDefaultModel, sizeof nm) == 0;
+  return 0;
+}
+
+extern "C" int cmpc_batch_get_model(const cmpc_batch* h, cmpc_model* out) {
+  if (!h || !out) return -1;
+  *out = h->model;
+  return 0;
 }
 
 extern "C" int cmpc_batch_set_refine(cmpc_batch* h, int on) {
@@ -363,7 +414,7 @@ extern "C" int cmpc_batch_estimate_due(cmpc_batch* h, float* d_est, const float*
     return -1;
   }
   hipError_t e = cmpc::launch_estimate(d_est, d_logs, d_fext3, d_time, sim_time, d_records, h->kp.rec_words,
-                                       d_fext6, h->d_gauss, batch, h->stream, nullptr, d_due);
+                                       d_fext6, h->d_gauss, batch, h->stream, h->kp.mdl, nullptr, d_due);
   if (e != hipSuccess) return fail("launch_estimate", e);
   return 0;
 }
@@ -377,7 +428,7 @@ extern "C" int cmpc_batch_estimate(cmpc_batch* h, float* d_est, const float* d_l
     return -1;
   }
   hipError_t e = cmpc::launch_estimate(d_est, d_logs, d_fext3, d_time, sim_time, d_records,
-                                       h->kp.rec_words, d_fext6, h->d_gauss, batch, h->stream);
+                                       h->kp.rec_words, d_fext6, h->d_gauss, batch, h->stream, h->kp.mdl);
   if (e != hipSuccess) return fail("launch_estimate", e);
   return 0;
 }
@@ -417,7 +468,7 @@ extern "C" int cmpc_batch_rollout(cmpc_batch* h, float* d_loco, const float* d_r
   }
   cmpc::LocoParams kp{h->kp.dt, 1, 0.f, h->kp.N, h->kp.rec_words, 0.f, 0.f, 0.f, 0.f, 0.f, h->kp.out_cols};
   hipError_t e = cmpc::launch_rollout(d_loco, d_records, d_forces, d_xi6, d_due, kp, h->kp.dt,
-                                      batch, h->stream);
+                                      h->kp.mdl, batch, h->stream);
   if (e != hipSuccess) return fail("launch_rollout", e);
   return 0;
 }
@@ -640,8 +691,8 @@ extern "C" int cmpc_batch_evaluate(cmpc_batch* h, const float* d_records, const 
     g_last_error = "cmpc_batch_evaluate: the handle keeps fewer than N output steps, its forces are not a full solution";
     return -3;
   }
-  const hipError_t e = cmpc::launch_evaluate(d_records, d_forces, batch, h->kp, (double)h->prm.alpha, d_xpred,
-                                             d_cert, h->stream);
+  const hipError_t e = cmpc::launch_evaluate(d_records, d_forces, batch, h->kp, (double)h->prm.alpha,
+                                             h->model.inertia, d_xpred, d_cert, h->stream);
   if (e != hipSuccess) return fail("launch_evaluate", e);
   return 0;
 }
@@ -715,6 +766,7 @@ struct SingleState {
   std::vector<float> traj;
   std::vector<unsigned char> gait;
   int max_iterations = 0, use_jcqp = 0;
+  cmpc_model model = {12.0, {0.07, 0.26, 0.242}};  // cmpc_set_model: the next solve's model
   double rho = 0, sigma = 0, solver_alpha = 0, terminate = 0;
   // solve_mpc state
   std::vector<double> q_soln;
@@ -784,7 +836,7 @@ int solve_single_device(SingleState& s, const float* rec, int N, float* forces, 
       hipSuccess)
     return fail("H2D", e);
   if ((e = cmpc::launch_estimate(s.d_est, nullptr, h->d_rec + rw, h->d_rec + rw + 1, 0.f, h->d_rec, (int)rw,
-                                 nullptr, h->d_gauss, 1, h->stream, d_out + 12 * N + 1)) != hipSuccess)
+                                 nullptr, h->d_gauss, 1, h->stream, h->kp.mdl, d_out + 12 * N + 1)) != hipSuccess)
     return fail("launch_estimate", e);
   if (s.use_jcqp == 1 || s.use_jcqp == 2) {
     // use_jcqp == 1 (SolverMPC.cpp:818-838, 1057-1062): ADMM over the full QP; use_jcqp == 2
@@ -826,6 +878,10 @@ void solve_single(SingleState& s) {
       return;
     }
     s.h_horizon = N;
+  }
+  if (std::memcmp(&s.model, &s.h->model, sizeof(s.model)) != 0 && cmpc_batch_set_model(s.h, &s.model) != 0) {
+    std::fprintf(stderr, "[cmpc] %s\n", cmpc_last_error());
+    return;
   }
   cmpc_params prm = s.cfg;
   for (int i = 0; i < 12; i++) prm.weights[i] = s.weights[i];
@@ -917,6 +973,17 @@ extern "C" void update_solver_settings(int max_iter, double rho, double sigma, d
   g.terminate = terminate;
   g.use_jcqp = use_jcqp > 1.5 ? 2 : (use_jcqp > 0.5 ? 1 : 0);
   // use_jcqp == 1 / 2 run the ADMM kernel (full / reduced QP)
+}
+
+extern "C" int cmpc_set_model(const cmpc_model* m) {
+  const cmpc_model nm = m ? *m : kDefaultModel;
+  if (!model_ok(nm)) {
+    g_last_error = "cmpc_set_model: mass and inertia must be finite and positive";
+    return -2;
+  }
+  std::lock_guard<std::mutex> lk(g.mu);
+  g.model = nm;  // the handle gets it in the next update_problem_data* call (solve_single)
+  return 0;
 }
 
 extern "C" void update_problem_data_floats(float* p, float* v, float* q, float* w, float* r, float roll,

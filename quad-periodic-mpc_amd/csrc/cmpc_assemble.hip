@@ -321,13 +321,14 @@ __global__ __launch_bounds__(256) void cmpc_rollout_kernel(float* __restrict__ l
                                                            const float* __restrict__ forces,
                                                            const float* __restrict__ xi6,
                                                            const uint8_t* __restrict__ due,
-                                                           LocoParams lp, float dt, int batch) {
+                                                           LocoParams lp, float dt, KModel mdl,
+                                                           int batch) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= batch || (due && !due[i])) return;
   const float* rec = recs + (size_t)i * lp.rec_words;
   const float* u = forces + (size_t)i * lp.out_cols;  // step 0: 12 forces, leg * 3 + axis
   Model md;
-  make_model(rec, dt, md);
+  make_model(rec, dt, mdl, md);
   float BdtT[12][16];
 #pragma unroll
   for (int c = 0; c < 12; c++) make_bdt<12>(rec, md, c, BdtT);
@@ -451,10 +452,10 @@ hipError_t launch_assemble(float* d_loco, const LocoParams& lp, float* d_recs, u
 
 hipError_t launch_rollout(float* d_loco, const float* d_recs, const float* d_forces,
                           const float* d_xi6, const uint8_t* d_due, const LocoParams& lp, float dt,
-                          int batch, hipStream_t stream) {
+                          const KModel& mdl, int batch, hipStream_t stream) {
   if (batch <= 0) return hipSuccess;
   hipLaunchKernelGGL(cmpc_rollout_kernel, dim3((batch + 255) / 256), dim3(256), 0, stream, d_loco,
-                     d_recs, d_forces, d_xi6, d_due, lp, dt, batch);
+                     d_recs, d_forces, d_xi6, d_due, lp, dt, mdl, batch);
   return hipGetLastError();
 }
 

@@ -311,7 +311,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
     for (int t = v; t < nfs; t += 64) sh.cmask[t] = 0;
   }
   Model md;
-  make_model(srec, P.dt, md);
+  make_model(srec, P.dt, P.mdl, md);
   make_bdt<64>(srec, md, v, sh.u.BdtT);
   CondGeo cg;
   make_cond_geo<true>(srec, md, cg);

@@ -9,8 +9,10 @@
 //     recursions that build the reduced qH / qg (SolverMPC.cpp:806-814) without ever forming
 //     A_qp, B_qp or the dense 13N x 13N weight matrix S.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
+#include <tuple>
 #include <type_traits>
 
 #include "cmpc_kernels.h"
@@ -244,6 +246,7 @@ struct Model {
   float R[9];      // body rotation (Eigen toRotationMatrix of q, w-first); R_yaw = R (RobotState.cpp:44)
   float n1r[9];    // N1[0..2][6..8] = dt * R^T
   float dt, dth, xdrag;  // dt, dt^2/2, x_drag (A_c(11,9), SolverMPC.cpp:277)
+  float ib[3], im;       // body inertia and 1/m of the handle's model (KModel; uniform)
 };
 
 // y = N1 x   (13-vectors)
@@ -362,10 +365,11 @@ struct StepProj {
   float w[3], p[3];
 };
 
-// I_world^-1 = (R I_body R')^-1 by cofactors; m = 12 RobotState.h:26,
-// I_body = diag(.07, .26, .242) RobotState.h:25, I_world = R I_body R^T SolverMPC.cpp:593
+// I_world^-1 = (R I_body R')^-1 by cofactors; I_body = diag(md.ib), the handle's model (the
+// reference's literal diag(.07, .26, .242), RobotState.h:25, is the default),
+// I_world = R I_body R^T SolverMPC.cpp:593
 __device__ __forceinline__ void make_iinv(const Model& md, float* Ii) {
-  const float Ib0 = .07f, Ib1 = 0.26f, Ib2 = 0.242f;
+  const float Ib0 = md.ib[0], Ib1 = md.ib[1], Ib2 = md.ib[2];
   float Iw[9];
 #pragma unroll
   for (int i = 0; i < 3; i++)
@@ -401,7 +405,7 @@ __device__ __forceinline__ void make_cond_geo(RecPtr rec, const Model& md, CondG
 // the step's projection of z
 __device__ __forceinline__ void step_proj(const Model& md, const CondGeo& cg, const float* z, StepProj& pj) {
   const float dt2 = 2.f * md.dt, dtq = 2.f * md.dth, dtc = md.dt * md.dt * md.dt / 3.f;  // 2 dt, 2 dt^2/2, 2 dt^3/6
-  const float im = 1.f / 12.0f;
+  const float im = md.im;
   float q[3];
 #pragma unroll
   for (int i = 0; i < 3; i++)
@@ -492,8 +496,49 @@ __device__ __forceinline__ void step_entries(const Model& md, const CondGeo& cg,
 #endif
 }
 
-// quaternion (w,x,y,z) -> rotation matrix, as Eigen's toRotationMatrix (RobotState.cpp:36)
-__device__ __forceinline__ void make_model(const float* __restrict__ rec, float dt, Model& md) {
+// A word of the kernel's argument segment re-read where it is used: a scalar load at byte offset
+// `off` behind a pointer the optimiser cannot see through. An argument read the plain way is loaded
+// at kernel entry and holds its SGPRs until its last use (in a persistent kernel: throughout); the
+// builds at their register caps spill for that. Used for the robot model's values, which the
+// solver builds need at the head of an instance (fp32) and in the refinement (fp64) only.
+template <typename T>
+__device__ __forceinline__ T karg_late(int off) {
+  typedef const __attribute__((address_space(4))) char* kptr;
+  kptr p = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return *reinterpret_cast<const __attribute__((address_space(4))) T*>(p + off);
+}
+static_assert(alignof(KParams) == 8 && offsetof(KParams, mdl) % 8 == 0, "kernarg offsets of the model");
+// the model's fp32 values / fp64 reciprocals as one vector each: one scalar load (x4 / x8 dwords)
+typedef float kf32x4 __attribute__((ext_vector_type(4), aligned(4)));
+typedef double kf64x4 __attribute__((ext_vector_type(4), aligned(8)));
+static_assert(offsetof(KModel, ib) == 0 && offsetof(KModel, im) == 12 && offsetof(KModel, iinv64) == 16 &&
+              offsetof(KModel, im64) == 40, "KModel = {ib[3], im} {iinv64[3], im64}");
+
+// Byte offset and type of argument I of a kernel in its argument segment, from the kernel's own
+// signature (K = decltype(&kernel)): every argument lies at its natural alignment
+template <int I, class K>
+struct KArg;
+template <int I, class... A>
+struct KArg<I, void (*)(A...)> {
+  using type = std::tuple_element_t<I, std::tuple<A...>>;
+  static constexpr int offset() {
+    constexpr size_t sz[] = {sizeof(A)...}, al[] = {alignof(A)...};
+    size_t off = 0;
+    for (int i = 0; i <= I; i++) {
+      off = (off + al[i] - 1) / al[i] * al[i];
+      if (i < I) off += sz[i];
+    }
+    return (int)off;
+  }
+};
+
+// quaternion (w,x,y,z) -> rotation matrix, as Eigen's toRotationMatrix (RobotState.cpp:36).
+// MOFF >= 0: the byte offset of the kernel's KModel in its argument segment; the model's fp32
+// values are then read through karg_late, per instance, instead of from km.
+template <int MOFF = -1>
+__device__ __forceinline__ void make_model(const float* __restrict__ rec, float dt, const KModel& km,
+                                           Model& md) {
   const float qw = rec[CMPC_REC_Q + 0], qx = rec[CMPC_REC_Q + 1], qy = rec[CMPC_REC_Q + 2],
               qz = rec[CMPC_REC_Q + 3];
   const float tx = 2.f * qx, ty = 2.f * qy, tz = 2.f * qz;
@@ -506,6 +551,18 @@ __device__ __forceinline__ void make_model(const float* __restrict__ rec, float 
   md.dt = dt;
   md.dth = dt * dt * 0.5f;
   md.xdrag = rec[CMPC_REC_XDRAG];
+  if constexpr (MOFF >= 0) {
+    const kf32x4 m4 = karg_late<kf32x4>(MOFF);
+    md.ib[0] = m4.x;
+    md.ib[1] = m4.y;
+    md.ib[2] = m4.z;
+    md.im = m4.w;
+  } else {
+    md.ib[0] = km.ib[0];
+    md.ib[1] = km.ib[1];
+    md.ib[2] = km.ib[2];
+    md.im = km.im;
+  }
 #pragma unroll
   for (int i = 0; i < 3; i++)
 #pragma unroll
@@ -515,7 +572,7 @@ __device__ __forceinline__ void make_model(const float* __restrict__ rec, float 
 // Bdt[s][c] -> BdtT[c][s]: thread c < 12 (c = 3 leg + axis) builds column c, every row s
 // unrolled (constant indices only: a row-strided mapping turned the R lookups into a private
 // array on scratch). ct_ss_mats B_c rows 6..11: I_world^-1 [r]x, I/m; SolverMPC.cpp:267-276,
-// m = 12 RobotState.h:26, I_body = diag(.07, .26, .242) RobotState.h:25;
+// m and I_body of the handle's model (defaults 12, diag(.07, .26, .242): RobotState.h:25-26);
 // I_world = R I_body R^T, SolverMPC.cpp:593.
 template <int NT>
 __device__ __forceinline__ void make_bdt(const float* __restrict__ rec, const Model& md, int tid,
@@ -524,7 +581,7 @@ __device__ __forceinline__ void make_bdt(const float* __restrict__ rec, const Mo
   if (tid < 12) {
     float Ii[9];
     make_iinv(md, Ii);
-    const float im = 1.f / 12.0f;
+    const float im = md.im;
     const float dt = md.dt, dt2 = md.dth, dt3 = md.dt * md.dt * md.dt / 6.f;
     const int c = tid;
     const int b = c / 3, a = c - 3 * (c / 3);

@@ -26,7 +26,7 @@ __device__ void condense_one(const float* __restrict__ rec, const KParams& P, Sh
   const int n = 12 * N;
   for (int t = tid; t < 12 * N; t += NTG) sh.traj[t] = rec[CMPC_REC_HDR + t];
   Model md;
-  make_model(rec, P.dt, md);
+  make_model(rec, P.dt, P.mdl, md);
   make_bdt<NTG>(rec, md, tid, sh.BdtT);
   CondGeo cg;
   make_cond_geo<true>(rec, md, cg);

@@ -192,9 +192,10 @@ __device__ __forceinline__ void fft_stage(const double2* __restrict__ in, const 
 }
 
 // residual of ConvexMPCLocomotion.cpp:639-771 for one instance (one thread)
-__device__ void residual(const float* __restrict__ lg, const float* __restrict__ rec, float f_ext[6]) {
+// (mdl: I_body's three moments and 1/m of the handle's model)
+__device__ void residual(const float* __restrict__ lg, const float* __restrict__ rec, float4 mdl, float f_ext[6]) {
   const float* R = lg + CMPC_LOG_ROT;  // R_yaw of the logged step, row-major
-  const float Ib[3] = {0.07f, 0.26f, 0.242f};
+  const float Ib[3] = {mdl.x, mdl.y, mdl.z};
   float Iw[9];
 #pragma unroll
   for (int i = 0; i < 3; i++)
@@ -228,9 +229,9 @@ __device__ void residual(const float* __restrict__ lg, const float* __restrict__
       }
       tq[i] += m0 * u0 + m1 * u1 + m2 * u2;
     }
-    fs[0] += (1.f / 12.f) * u0;
-    fs[1] += (1.f / 12.f) * u1;
-    fs[2] += (1.f / 12.f) * u2;
+    fs[0] += mdl.w * u0;
+    fs[1] += mdl.w * u1;
+    fs[2] += mdl.w * u2;
   }
   // A_prev x_prev: rows 6..10 are zero; row 11 = x_drag * v_x + x(12)
   const float ax11 = lg[CMPC_LOG_XDRAG] * lg[CMPC_LOG_LIN + 0] + (-9.81f);
@@ -250,13 +251,13 @@ __device__ void residual(const float* __restrict__ lg, const float* __restrict__
 
 // One estimator step of instance blockIdx.x. DUE (cmpc_batch_estimate_due): the workgroup of an
 // instance that is not due returns before its first barrier, LDS write or global access other than
-// the due byte. The unmasked kernel below is the DUE = false body under its unchanged signature.
+// the due byte. The unmasked kernel below is the DUE = false body without the due argument.
 template <bool DUE>
 __device__ __forceinline__ void estimate_step(
     float* __restrict__ est, const float* __restrict__ logs, const float* __restrict__ fext3,
     const float* __restrict__ times, float sim_time, float* __restrict__ recs, int rec_words,
     float* __restrict__ fext6, const float* __restrict__ gauss, int batch, float* __restrict__ fest_out,
-    const uint8_t* __restrict__ due) {
+    const uint8_t* __restrict__ due, float4 mdl) {
   __shared__ SharedE sh;
   const int inst = blockIdx.x;
   if (inst >= batch) return;
@@ -269,7 +270,7 @@ __device__ __forceinline__ void estimate_step(
     float f3;
     if (logs) {
       float fe[6];
-      residual(logs + (size_t)inst * CMPC_LOG_WORDS, rec, fe);
+      residual(logs + (size_t)inst * CMPC_LOG_WORDS, rec, mdl, fe);
       f3 = fe[3];
       if (fext6) {
 #pragma unroll
@@ -385,17 +386,19 @@ __device__ __forceinline__ void estimate_step(
 __global__ __launch_bounds__(NT) void cmpc_estimate_kernel(
     float* __restrict__ est, const float* __restrict__ logs, const float* __restrict__ fext3,
     const float* __restrict__ times, float sim_time, float* __restrict__ recs, int rec_words,
-    float* __restrict__ fext6, const float* __restrict__ gauss, int batch, float* __restrict__ fest_out) {
+    float* __restrict__ fext6, const float* __restrict__ gauss, int batch, float* __restrict__ fest_out,
+    float4 mdl) {
   estimate_step<false>(est, logs, fext3, times, sim_time, recs, rec_words, fext6, gauss, batch, fest_out,
-                       nullptr);
+                       nullptr, mdl);
 }
 
 __global__ __launch_bounds__(NT) void cmpc_estimate_due_kernel(
     float* __restrict__ est, const float* __restrict__ logs, const float* __restrict__ fext3,
     const float* __restrict__ times, float sim_time, float* __restrict__ recs, int rec_words,
     float* __restrict__ fext6, const float* __restrict__ gauss, int batch, float* __restrict__ fest_out,
-    const uint8_t* __restrict__ due) {
-  estimate_step<true>(est, logs, fext3, times, sim_time, recs, rec_words, fext6, gauss, batch, fest_out, due);
+    const uint8_t* __restrict__ due, float4 mdl) {
+  estimate_step<true>(est, logs, fext3, times, sim_time, recs, rec_words, fext6, gauss, batch, fest_out, due,
+                      mdl);
 }
 
 }  // namespace
@@ -403,14 +406,15 @@ __global__ __launch_bounds__(NT) void cmpc_estimate_due_kernel(
 hipError_t launch_estimate(float* d_est, const float* d_logs, const float* d_fext3,
                            const float* d_time, float sim_time, float* d_records, int rec_words,
                            float* d_fext6, const float* d_gauss, int batch, hipStream_t stream,
-                           float* d_fest_out, const uint8_t* d_due) {
+                           const KModel& mdl, float* d_fest_out, const uint8_t* d_due) {
   if (batch <= 0) return hipSuccess;
+  const float4 m4 = make_float4(mdl.ib[0], mdl.ib[1], mdl.ib[2], mdl.im);  // read by the residual only
   if (d_due)
     hipLaunchKernelGGL(cmpc_estimate_due_kernel, dim3(batch), dim3(NT), 0, stream, d_est, d_logs, d_fext3,
-                       d_time, sim_time, d_records, rec_words, d_fext6, d_gauss, batch, d_fest_out, d_due);
+                       d_time, sim_time, d_records, rec_words, d_fext6, d_gauss, batch, d_fest_out, d_due, m4);
   else
     hipLaunchKernelGGL(cmpc_estimate_kernel, dim3(batch), dim3(NT), 0, stream, d_est, d_logs, d_fext3,
-                       d_time, sim_time, d_records, rec_words, d_fext6, d_gauss, batch, d_fest_out);
+                       d_time, sim_time, d_records, rec_words, d_fext6, d_gauss, batch, d_fest_out, m4);
   return hipGetLastError();
 }
 

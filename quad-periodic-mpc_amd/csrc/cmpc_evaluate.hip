@@ -68,7 +68,8 @@ __device__ __forceinline__ double bfly_max(double v) {
 
 __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restrict__ d_recs,
                                                            const float* __restrict__ d_forces, int batch,
-                                                           KParams P, double alpha,
+                                                           KParams P, double alpha, double ib0,
+                                                           double ib1, double ib2,
                                                            float* __restrict__ d_xpred,
                                                            double* __restrict__ d_cert) {
   __shared__ EvalShared sh;
@@ -79,6 +80,7 @@ __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restri
   const float* __restrict__ rec = d_recs + (size_t)inst * P.rec_words;
   const float* __restrict__ uin = d_forces + (size_t)inst * 12 * N;
   const double dt = P.dt64, dth = P.dth64, dt3 = P.dt3_64;
+  const double im64 = P.mdl.im64;  // 1 / m of the handle's model
   double* scr = sh.scr;
 
   // ---- 0: forces and traj into LDS (sum of u^2 on the way), the instance's matrices and x_0
@@ -91,7 +93,8 @@ __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restri
   }
   if (lane == 0) {
     // R (Eigen toRotationMatrix, RobotState.cpp:36) and I_world = R I_body R' (SolverMPC.cpp:593;
-    // I_body: RobotState.h:25) in fp64 from the fp32 quaternion; the inverse by cofactors
+    // I_body = diag(ib0, ib1, ib2), the handle's model; RobotState.h:25 is the default) in fp64
+    // from the fp32 quaternion; the inverse by cofactors
     const double qw = rec[CMPC_REC_Q + 0], qx = rec[CMPC_REC_Q + 1], qy = rec[CMPC_REC_Q + 2],
                  qz = rec[CMPC_REC_Q + 3];
     double R[9];
@@ -103,8 +106,8 @@ __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restri
     for (int i = 0; i < 3; i++)
 #pragma unroll
       for (int j = 0; j < 3; j++)
-        Iw[3 * i + j] = R[3 * i] * 0.07 * R[3 * j] + R[3 * i + 1] * 0.26 * R[3 * j + 1] +
-                        R[3 * i + 2] * 0.242 * R[3 * j + 2];
+        Iw[3 * i + j] = R[3 * i] * ib0 * R[3 * j] + R[3 * i + 1] * ib1 * R[3 * j + 1] +
+                        R[3 * i + 2] * ib2 * R[3 * j + 2];
     const double c00 = Iw[4] * Iw[8] - Iw[5] * Iw[7];
     const double c10 = Iw[5] * Iw[6] - Iw[3] * Iw[8];
     const double c20 = Iw[3] * Iw[7] - Iw[4] * Iw[6];
@@ -161,7 +164,7 @@ __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restri
         sq[i] = zero ? 0.0 : tsk[3 + i];
       }
       // w = B_c u_k + Q_c f: w[6:9] = I_world^-1 t, w[9:12] = s / m (+ f_est(3) into row 9)
-      const double w9 = sq[0] * (1.0 / 12.0) + scr[19];
+      const double w9 = sq[0] * im64 + scr[19];
       double c;
       if (j < 3 || (j >= 6 && j < 9)) {
         c = 0.0;
@@ -173,11 +176,11 @@ __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restri
       } else if (j == 3 || j == 9) {
         c = ((j == 3) ? dth : dt) * w9;
       } else if (j == 4 || j == 10) {
-        c = ((j == 4) ? dth : dt) * sq[1] * (1.0 / 12.0);
+        c = ((j == 4) ? dth : dt) * sq[1] * im64;
       } else if (j == 5) {
-        c = dth * sq[2] * (1.0 / 12.0) + dt3 * xd * w9 + dth * grav;
+        c = dth * sq[2] * im64 + dt3 * xd * w9 + dth * grav;
       } else {
-        c = dt * sq[2] * (1.0 / 12.0) + dth * xd * w9 + dt * grav;
+        c = dt * sq[2] * im64 + dth * xd * w9 + dt * grav;
       }
       sh.st[t] = c;
     }
@@ -255,11 +258,11 @@ __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restri
         ev += Ii[3 * i + m] * nu;
       }
     } else if (i == 3) {
-      ev = (dt * lm[9] + dth * (lm[3] + xd * lm[11]) + dt3 * xd * lm[5]) * (1.0 / 12.0);
+      ev = (dt * lm[9] + dth * (lm[3] + xd * lm[11]) + dt3 * xd * lm[5]) * im64;
     } else if (i == 4) {
-      ev = (dt * lm[10] + dth * lm[4]) * (1.0 / 12.0);
+      ev = (dt * lm[10] + dth * lm[4]) * im64;
     } else {
-      ev = (dt * lm[11] + dth * lm[5]) * (1.0 / 12.0);
+      ev = (dt * lm[11] + dth * lm[5]) * im64;
     }
     sh.ts[t] = ev;
   }
@@ -327,10 +330,11 @@ __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restri
 }  // namespace
 
 hipError_t launch_evaluate(const float* d_recs, const float* d_forces, int batch, const KParams& P,
-                           double alpha, float* d_xpred, double* d_cert, hipStream_t stream) {
+                           double alpha, const double* ib64, float* d_xpred, double* d_cert,
+                           hipStream_t stream) {
   if (batch <= 0) return hipSuccess;
   hipLaunchKernelGGL(cmpc_evaluate_kernel, dim3(batch), dim3(64), 0, stream, d_recs, d_forces, batch, P,
-                     alpha, d_xpred, d_cert);
+                     alpha, ib64[0], ib64[1], ib64[2], d_xpred, d_cert);
   return hipGetLastError();
 }
 

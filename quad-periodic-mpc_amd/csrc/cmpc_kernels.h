@@ -21,6 +21,17 @@ inline int diag_knob(const char* name, int dflt) {
 #endif
 }
 
+// Kernel-side form of cmpc_model: the values the kernels use, derived on the host once
+// (make_kmodel, cmpc_abi.cpp). The fp32 kernels take (float) of each field, the fp64 refinement
+// the reciprocals of the doubles themselves: the mix of literals the code had when the model was
+// m = 12, I_body = diag(.07, .26, .242) (RobotState.h:25-26), so that model gives the same bits.
+struct KModel {
+  float ib[3];       // (float) inertia[i]
+  float im;          // 1.f / (float) mass
+  double iinv64[3];  // 1.0 / inertia[i]
+  double im64;       // 1.0 / mass
+};
+
 // Kernel-side copy of cmpc_params (by value, lands in SGPRs).
 struct KParams {
   float dt;
@@ -34,8 +45,11 @@ struct KParams {
   int refine;      // wide classes: one fp64 refinement step of the converged active set (N > 10)
   int out_cols;    // forces written per instance: 12 x the leading horizon steps kept
                    // (cmpc_batch_set_output_steps; 12 N by default)
+  int mdl_default; // host side only: mdl is the default robot's (the launchers then take the builds
+                   // with the model as literals, where there is one)
   // the step's fp64 powers for that refinement (scalar registers, not per-lane conversions)
   double dt64, dth64, dt3_64;  // dt, dt^2 / 2, dt^3 / 6
+  KModel mdl;      // the handle's robot model (cmpc_batch_set_model)
 };
 
 // Kernel-side copy of cmpc_loco_params + the handle's horizon / record stride.
@@ -159,7 +173,7 @@ constexpr int kGaussTaps = 2 * kGaussR7 + 1 + 2 * kGaussR27 + 1;
 hipError_t launch_estimate(float* d_est, const float* d_logs, const float* d_fext3,
                            const float* d_time, float sim_time, float* d_records, int rec_words,
                            float* d_fext6, const float* d_gauss, int batch, hipStream_t stream,
-                           float* d_fest_out = nullptr, const uint8_t* d_due = nullptr);
+                           const KModel& mdl, float* d_fest_out = nullptr, const uint8_t* d_due = nullptr);
 // batched input assembly (cmpc_assemble.hip): one control tick per instance
 hipError_t launch_assemble(float* d_loco, const LocoParams& lp, float* d_recs, uint8_t* d_due,
                            int batch, hipStream_t stream);
@@ -169,16 +183,18 @@ hipError_t launch_expand(const float* d_compact, float* d_recs, int batch, int N
 // single-rigid-body step of every due instance with its solved step-0 forces (cmpc_assemble.hip)
 hipError_t launch_rollout(float* d_loco, const float* d_recs, const float* d_forces,
                           const float* d_xi6, const uint8_t* d_due, const LocoParams& lp, float dt,
-                          int batch, hipStream_t stream);
+                          const KModel& mdl, int batch, hipStream_t stream);
 // parity hook and JCQP condensation: full (nothing eliminated) qH [12N x 12N] / qg [12N] per
 // instance (cmpc_condense.hip)
 hipError_t launch_condense(const float* d_recs, int batch, const KParams& P, float* d_H, float* d_g,
                            hipStream_t stream);
 // fp64 prediction, cost and optimality gap of given forces [batch x 12N] (cmpc_evaluate.hip), one
 // wavefront per instance; alpha = the force regularisation (KParams holds 2 alpha in fp32 only).
+// ib64 = the body inertia's three doubles (KParams holds their reciprocals only).
 // d_xpred / d_cert: either may be NULL
 hipError_t launch_evaluate(const float* d_recs, const float* d_forces, int batch, const KParams& P,
-                           double alpha, float* d_xpred, double* d_cert, hipStream_t stream);
+                           double alpha, const double* ib64, float* d_xpred, double* d_cert,
+                           hipStream_t stream);
 
 // use_jcqp == 1 / 2: batched JCQP ADMM over the full / reduced condensed QP (cmpc_admm.hip).
 // Instances whose QP has n > 120 variables run on nslabs persistent workgroups with M in

@@ -90,6 +90,19 @@ extern "C" int cmpc_multi_rows(const cmpc_multi* m, int batch, int* rows) {
   return 0;
 }
 
+extern "C" int cmpc_multi_set_model(cmpc_multi* m, const cmpc_model* model) {
+  if (!m) return fail("cmpc_multi_set_model: bad arguments");
+  // checked on the root's handle first: a bad model changes no handle
+  for (auto& p : m->parts) {
+    if (!p.h) continue;
+    if (const int r = cmpc_batch_set_model(p.h, model); r != 0) {
+      fail(std::string("cmpc_batch_set_model: ") + cmpc_last_error());
+      return r;
+    }
+  }
+  return 0;
+}
+
 extern "C" void cmpc_multi_destroy(cmpc_multi* m) {
   if (!m) return;
   for (auto& p : m->parts) {

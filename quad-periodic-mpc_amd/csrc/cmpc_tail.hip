@@ -170,7 +170,9 @@ __device__ __forceinline__ float group_sum(float v) {
   return v;
 }
 
-template <int T>
+// POFF: byte offset of the kernel's KParams argument in its argument segment (make_model reads the
+// model's values there, late)
+template <int T, int POFF>
 __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KParams& P,
                                         SharedT<T>& sh, float* __restrict__ fout,
                                         uint8_t* __restrict__ st_out, int32_t* __restrict__ it_out,
@@ -240,7 +242,7 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
   }
   if (v < nfs) sh.cmask[v] = 0;
   Model md;
-  make_model(srec, P.dt, md);
+  make_model<POFF + (int)offsetof(KParams, mdl)>(srec, P.dt, P.mdl, md);
   make_bdt<64>(srec, md, v, sh.u.BdtT);
   tsync();
   if (v < N) {
@@ -1006,6 +1008,9 @@ __global__ __launch_bounds__(64, CMPC_TAIL_WAVES_PER_EU) void cmpc_solve_t_kerne
     const float* __restrict__ recs, KParams P, float* __restrict__ forces, uint8_t* __restrict__ status,
     int32_t* __restrict__ iters, const int* __restrict__ in_list, const int* __restrict__ in_count,
     int* __restrict__ ovf_list, int* __restrict__ ovf_count, int first) {
+  using KP = KArg<1, decltype(&cmpc_solve_t_kernel)>;  // the KParams argument, located by this signature
+  static_assert(std::is_same<KP::type, KParams>::value, "argument 1 is the KParams");
+  constexpr int kPoff = KP::offset();
   __shared__ SharedT<kTailRows> sh;
 #if CMPC_TAIL_PRIO > 0
   __builtin_amdgcn_s_setprio(CMPC_TAIL_PRIO);
@@ -1013,8 +1018,8 @@ __global__ __launch_bounds__(64, CMPC_TAIL_WAVES_PER_EU) void cmpc_solve_t_kerne
   const int b = first + (int)blockIdx.x;
   if (b >= *in_count) return;
   const int t = in_list[b];
-  solve_t<kTailRows>(recs + (size_t)t * P.rec_words, P, sh, forces + (size_t)t * P.out_cols, status + t,
-                     iters ? iters + t : nullptr, ovf_list, ovf_count, t);
+  solve_t<kTailRows, kPoff>(recs + (size_t)t * P.rec_words, P, sh, forces + (size_t)t * P.out_cols,
+                            status + t, iters ? iters + t : nullptr, ovf_list, ovf_count, t);
 }
 
 // The entries past a predicted grid (normally none: its few workgroups exit at once), grid-stride.
@@ -1022,12 +1027,15 @@ __global__ __launch_bounds__(64, CMPC_TAIL_WAVES_PER_EU) void cmpc_solve_t_rest_
     const float* __restrict__ recs, KParams P, float* __restrict__ forces, uint8_t* __restrict__ status,
     int32_t* __restrict__ iters, const int* __restrict__ in_list, const int* __restrict__ in_count,
     int* __restrict__ ovf_list, int* __restrict__ ovf_count, int first) {
+  using KP = KArg<1, decltype(&cmpc_solve_t_rest_kernel)>;  // the KParams argument, located by this signature
+  static_assert(std::is_same<KP::type, KParams>::value, "argument 1 is the KParams");
+  constexpr int kPoff = KP::offset();
   __shared__ SharedT<kTailRows> sh;
   const int count = *in_count;
   for (int b = first + (int)blockIdx.x; b < count; b += (int)gridDim.x) {
     const int t = in_list[b];
-    solve_t<kTailRows>(recs + (size_t)t * P.rec_words, P, sh, forces + (size_t)t * P.out_cols, status + t,
-                       iters ? iters + t : nullptr, ovf_list, ovf_count, t);
+    solve_t<kTailRows, kPoff>(recs + (size_t)t * P.rec_words, P, sh, forces + (size_t)t * P.out_cols,
+                              status + t, iters ? iters + t : nullptr, ovf_list, ovf_count, t);
     __builtin_amdgcn_wave_barrier();
     asm volatile("" ::: "memory");
   }
@@ -1042,6 +1050,9 @@ __global__ __launch_bounds__(64, CMPC_TAIL_WAVES_PER_EU) void cmpc_solve_t_self_
     const float* __restrict__ recs, int batch, KParams P, float* __restrict__ forces,
     uint8_t* __restrict__ status, int32_t* __restrict__ iters, int* __restrict__ ovf_list,
     int* __restrict__ ovf_count, int chunk) {
+  using KP = KArg<2, decltype(&cmpc_solve_t_self_kernel)>;  // the KParams argument, located by this signature
+  static_assert(std::is_same<KP::type, KParams>::value, "argument 2 is the KParams");
+  constexpr int kPoff = KP::offset();
   __shared__ SharedT<kTailRows> sh;
 #if CMPC_TAIL_PRIO > 0
   __builtin_amdgcn_s_setprio(CMPC_TAIL_PRIO);
@@ -1067,8 +1078,8 @@ __global__ __launch_bounds__(64, CMPC_TAIL_WAVES_PER_EU) void cmpc_solve_t_self_
       const int b = __ffsll((long long)m) - 1;
       m &= m - 1ull;
       const int t = c0 + b;
-      solve_t<kTailRows>(recs + (size_t)t * P.rec_words, P, sh, forces + (size_t)t * P.out_cols, status + t,
-                         iters ? iters + t : nullptr, ovf_list, ovf_count, t);
+      solve_t<kTailRows, kPoff>(recs + (size_t)t * P.rec_words, P, sh, forces + (size_t)t * P.out_cols,
+                                status + t, iters ? iters + t : nullptr, ovf_list, ovf_count, t);
       __builtin_amdgcn_wave_barrier();
       asm volatile("" ::: "memory");
     }

@@ -273,6 +273,37 @@ __device__ __forceinline__ int rli_pos(const int (&a)[RQ], int i) {
   (void)h;                                           \
   (void)r
 
+struct WideArgs {
+  const float* recs;
+  float* forces;
+  uint8_t* status;
+  int32_t* iters;
+  const int* in_list;
+  const int* in_count;
+  int* deq;
+  KParams P;
+  int base;  // persistent form: first list entry it takes (0, or the grid of a one-per-entry launch)
+};
+// byte offset of the kernel's KModel in its argument segment (WideArgs is the one argument): the
+// model's values are read there where they are used (karg_late), not held from kernel entry
+constexpr int kWideMdlOff = (int)(offsetof(WideArgs, P) + offsetof(KParams, mdl));
+// CMPC_WIDE_LITERAL = 1: the build of the default robot (m = 12, I_body = diag(.07, .26, .242),
+// RobotState.h:25-26) with the model as literals, as before the model was a parameter; the launcher
+// picks it when the handle's model is the default (KParams::mdl_default), so the default pays nothing
+// for the parameter. Built for the refining 96- and 120-column classes in both launch forms (N = 16
+// and N = 20 trot, the measured workloads); the model-reading build is the unit without the "d".
+#ifndef CMPC_WIDE_LITERAL
+#define CMPC_WIDE_LITERAL 0
+#endif
+// 1 / m in phases B and D of the refinement: the grouped load's value, held across the phases. The
+// 256-column build alone re-reads it at each use: at its 256-VGPR cap, holding it cost 20 B of
+// scratch per lane
+template <int NV>
+__device__ __forceinline__ double ref_im64(double grouped) {
+  if constexpr (NV > 192 && !CMPC_WIDE_LITERAL) return karg_late<double>(kWideMdlOff + (int)offsetof(KModel, im64));
+  else return grouped;
+}
+
 // Mixed-precision refinement of the converged active set, one step. With the working set W of the
 // dual active set, x minimises the fp32-condensed QP on the face {C_W x = b_W}; the minimiser of
 // the exact QP on that face is x - J2 J2' r, where r = H x + g is the exact QP's gradient at x and
@@ -324,6 +355,13 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
   double* scr = reinterpret_cast<double*>(&sh.P[G::O_RINV]);
   const int N = P.N;
   const double dt = P.dt64, dth = P.dth64, dt3 = P.dt3_64;
+  // the model's fp64 values: one grouped scalar load here, at the head of the refinement
+#if CMPC_WIDE_LITERAL
+  const double ii0 = 1.0 / 0.07, ii1 = 1.0 / 0.26, ii2 = 1.0 / 0.242, im64 = 1.0 / 12.0;
+#else
+  const kf64x4 m64 = karg_late<kf64x4>(kWideMdlOff + (int)offsetof(KModel, iinv64));
+  const double ii0 = m64.x, ii1 = m64.y, ii2 = m64.z, im64 = m64.w;  // 1 / I_body, 1 / m
+#endif
   const float* xs = sh.xs();
   // ---- A: per step and axis, sum_b r_b x u_b and sum_b u_b; R, I_w^-1 and the instance scalars
   if (!(CMPC_DIAG_REF_SKIP & 1)) {
@@ -393,8 +431,7 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
         val = rot(e / 3, e - 3 * (e / 3));
       } else {
         const int i = (e - 9) / 3, j = (e - 9) - 3 * ((e - 9) / 3);
-        val = rot(i, 0) * (1.0 / 0.07) * rot(j, 0) + rot(i, 1) * (1.0 / 0.26) * rot(j, 1) +
-              rot(i, 2) * (1.0 / 0.242) * rot(j, 2);
+        val = rot(i, 0) * ii0 * rot(j, 0) + rot(i, 1) * ii1 * rot(j, 1) + rot(i, 2) * ii2 * rot(j, 2);
       }
       scr[e] = val;
     } else if (t == G::NT - 19) {
@@ -425,7 +462,7 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
         const double* ts = scr + S0 + 12 * k;
         const double xd = scr[18];
         // w = B_c u_k (+ Q_c f: f_est(3) into row 9)
-        const double w9 = ts[3] * (1.0 / 12.0) + scr[19];
+        const double w9 = ts[3] * ref_im64<NV>(im64) + scr[19];
         double c;
         if (j < 3 || (j >= 6 && j < 9)) {
           // j < 3: dt^2/2 (R' w[6:9])_j; 6..8: dt w_j, w[6:9] = I_w^-1 t
@@ -438,11 +475,11 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
         } else if (j == 3 || j == 9) {
           c = ((j == 3) ? dth : dt) * w9;
         } else if (j == 4 || j == 10) {
-          c = ((j == 4) ? dth : dt) * ts[4] * (1.0 / 12.0);
+          c = ((j == 4) ? dth : dt) * ts[4] * ref_im64<NV>(im64);
         } else if (j == 5) {
-          c = dth * ts[5] * (1.0 / 12.0) + dt3 * xd * w9;
+          c = dth * ts[5] * ref_im64<NV>(im64) + dt3 * xd * w9;
         } else {
-          c = dt * ts[5] * (1.0 / 12.0) + dth * xd * w9;
+          c = dt * ts[5] * ref_im64<NV>(im64) + dth * xd * w9;
         }
         // X_d,k-1 (x0 for k = 0: [rpy, p, w, v], rpy as quat_to_rpy in fp32)
         auto vprev = [&](int i) -> double {
@@ -531,7 +568,7 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
         // fp64 operands were the refining builds' register peak and spilled the J rows' neighbours)
         const int ic = (i < 3) ? i : 0, il = (i < 3) ? 0 : i - 3;
         const double x3 = (i == 3) ? xd : 0.0;
-        const double e2 = (dt * mu[9 + il] + dth * (mu[3 + il] + x3 * mu[11]) + dt3 * x3 * mu[5]) * (1.0 / 12.0);
+        const double e2 = (dt * mu[9 + il] + dth * (mu[3 + il] + x3 * mu[11]) + dt3 * x3 * mu[5]) * ref_im64<NV>(im64);
         __builtin_amdgcn_sched_barrier(0);
         double e1 = 0.0;
 #pragma unroll
@@ -549,11 +586,11 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
             ev += Ii[3 * i + m] * nu;
           }
         } else if (i == 3) {
-          ev = (dt * mu[9] + dth * (mu[3] + xd * mu[11]) + dt3 * xd * mu[5]) * (1.0 / 12.0);
+          ev = (dt * mu[9] + dth * (mu[3] + xd * mu[11]) + dt3 * xd * mu[5]) * ref_im64<NV>(im64);
         } else if (i == 4) {
-          ev = (dt * mu[10] + dth * mu[4]) * (1.0 / 12.0);
+          ev = (dt * mu[10] + dth * mu[4]) * ref_im64<NV>(im64);
         } else {
-          ev = (dt * mu[11] + dth * mu[5]) * (1.0 / 12.0);
+          ev = (dt * mu[11] + dth * mu[5]) * ref_im64<NV>(im64);
         }
       }
     }
@@ -725,7 +762,12 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
     for (int i = t; i < 6 * nfs; i += G::NT) sh.cflag[i] = 0;
   }
   Model md;
-  make_model(srec, P.dt, md);
+#if CMPC_WIDE_LITERAL
+  constexpr KModel kLit{{.07f, 0.26f, 0.242f}, 1.f / 12.0f, {1.0 / 0.07, 1.0 / 0.26, 1.0 / 0.242}, 1.0 / 12.0};
+  make_model(srec, P.dt, kLit, md);
+#else
+  make_model<kWideMdlOff>(srec, P.dt, P.mdl, md);
+#endif
   make_bdt<G::NT>(srec, md, t, sh.BdtT());
   wbar();
   float wts[13];
@@ -1524,23 +1566,16 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
 #else
 #define CMPC_WIDE_VGPR_ATTR
 #endif
-struct WideArgs {
-  const float* recs;
-  float* forces;
-  uint8_t* status;
-  int32_t* iters;
-  const int* in_list;
-  const int* in_count;
-  int* deq;
-  KParams P;
-  int base;  // persistent form: first list entry it takes (0, or the grid of a one-per-entry launch)
-};
 
 // REFINE is part of the kernel's name: the refining and plain builds of a class live in different
 // units, and one instantiation name would let the linker keep only one of them
-template <int NV, bool PERSIST, bool REFINE>
+// (LIT, the literal-model build, is part of the name for the same reason)
+template <int NV, bool PERSIST, bool REFINE, bool LIT = (CMPC_WIDE_LITERAL != 0)>
 __global__ __launch_bounds__(WGeo<NV>::NT, CMPC_WIDE_WAVES_PER_EU) CMPC_WIDE_VGPR_ATTR void cmpc_solve_w_kernel(
     WideArgs A) {
+  // kWideMdlOff counts from the head of the argument segment: WideArgs is argument 0
+  using KA = KArg<0, decltype(&cmpc_solve_w_kernel<NV, PERSIST, REFINE, LIT>)>;
+  static_assert(std::is_same<typename KA::type, WideArgs>::value && KA::offset() == 0, "WideArgs leads the arguments");
   __shared__ SharedW<NV> sh;
 #if CMPC_WIDE_PRIO > 0
   // issue priority of this workgroup's waves over the class-1 waves sharing their SIMDs

@@ -25,13 +25,22 @@ hipError_t launch_wide_w120_r(const float* d_recs, const KParams& P, float* d_fo
 hipError_t launch_wide_w120_persist_r(const float* d_recs, const KParams& P, float* d_forces,
                                     uint8_t* d_status, int32_t* d_iters, const int* in_list,
                                     const int* in_count, int* deq, int grid, hipStream_t stream, int base);
+// the same two with the default robot's model as literals (cmpc_wide_w120rd.hip, cmpc_wide_w120prd.hip)
+hipError_t launch_wide_w120_r_lit(const float* d_recs, const KParams& P, float* d_forces, uint8_t* d_status,
+                                int32_t* d_iters, const int* in_list, const int* in_count, int* deq, int grid,
+                                hipStream_t stream, int base);
+hipError_t launch_wide_w120_persist_r_lit(const float* d_recs, const KParams& P, float* d_forces,
+                                        uint8_t* d_status, int32_t* d_iters, const int* in_list,
+                                        const int* in_count, int* deq, int grid, hipStream_t stream, int base);
 
 hipError_t launch_wide_w120(const float* d_recs, const KParams& P, float* d_forces, uint8_t* d_status,
                           int32_t* d_iters, const int* in_list, const int* in_count, int* deq, int grid,
                           hipStream_t stream, int base) {
   if (P.refine)
-    return deq ? launch_wide_w120_persist_r(d_recs, P, d_forces, d_status, d_iters, in_list, in_count, deq, grid, stream, base)
-               : launch_wide_w120_r(d_recs, P, d_forces, d_status, d_iters, in_list, in_count, nullptr, grid, stream, base);
+    return deq ? (P.mdl_default ? launch_wide_w120_persist_r_lit : launch_wide_w120_persist_r)(
+                     d_recs, P, d_forces, d_status, d_iters, in_list, in_count, deq, grid, stream, base)
+               : (P.mdl_default ? launch_wide_w120_r_lit : launch_wide_w120_r)(
+                     d_recs, P, d_forces, d_status, d_iters, in_list, in_count, nullptr, grid, stream, base);
   if (deq)  // persistent form: its own unit (compiled beside this kernel it spilled registers)
     return launch_wide_w120_persist(d_recs, P, d_forces, d_status, d_iters, in_list, in_count, deq, grid,
                                    stream, base);

@@ -262,9 +262,23 @@ class RootPipeline:
     def __init__(self, params, global_batch: int, chunks: Optional[int] = None, *, group=None,
                  device=None, src: int = 0, solve_fn=None, record_words: Optional[int] = None,
                  lanes: Optional[int] = None, out_steps: int = 0,
-                 root_share: Optional[float] = None, record_format: str = "full"):
+                 root_share: Optional[float] = None, record_format: str = "full", model=None,
+                 lane_device=None):
         from .records import compact_words, record_words as _rw
         self.params = params
+        # the robot model (records.make_model) of this rank's solver lanes, root and peers alike;
+        # None: the default. A solve_fn brings its own solver, so a model cannot be given with one
+        if model is not None and solve_fn is not None:
+            raise ValueError("model= applies to the pipeline's own solver lanes; a solve_fn sets its solver's model itself")
+        self.model = model
+        # lane_device: a staging and testing path, not a production one. The GPU of the pipeline's
+        # own solver lanes when this rank's buffers (device=) live elsewhere, i.e. host tensors
+        # exchanged over the gloo backend (two ranks on one GPU in the tests). Each piece's rows are
+        # copied to that GPU, solved there and copied back, with a device-wide synchronisation on
+        # either side of the solve (it stalls every other stream of that device): no overlap
+        if lane_device is not None and solve_fn is not None:
+            raise ValueError("lane_device= places the pipeline's own solver lanes; a solve_fn has none")
+        self.lane_device = torch.device(lane_device) if lane_device is not None else None
         self.N = params.horizon
         if record_format not in ("full", "compact"):
             raise ValueError(f"record_format {record_format!r}: 'full' or 'compact'")
@@ -319,7 +333,11 @@ class RootPipeline:
             import importlib
             solver_mod = importlib.import_module(__package__ + ".solver")
             nl = max(1, min(self.LANES if lanes is None else int(lanes), self.chunks))
-            if nl == 1:   # one lane: the caller's stream itself (no fork / join)
+            if self.lane_device is not None:   # staged lanes: each handle on a private stream
+                with torch.cuda.device(self.lane_device):
+                    self._solvers = [solver_mod.BatchSolver(params, max_batch=max(1, max(self.sizes)))
+                                     for _ in range(nl)]
+            elif nl == 1:   # one lane: the caller's stream itself (no fork / join)
                 self._solvers = [solver_mod.BatchSolver(params, max_batch=max(1, max(self.sizes)),
                                                         stream=torch.cuda.current_stream(dev))]
             else:
@@ -329,6 +347,8 @@ class RootPipeline:
             for sv in self._solvers:
                 if self.out_steps:
                     sv.set_output_steps(self.out_steps)
+                if model is not None:
+                    sv.set_model(model)
             self._solver = self._solvers[0]
 
     def _lane(self, c):
@@ -372,13 +392,34 @@ class RootPipeline:
             if self._solve_fn is not None:
                 from .records import expand_records
                 full.copy_(torch.from_numpy(expand_records(recs.cpu().numpy(), self.N, self.params.dt)))
+            elif self.lane_device is not None:
+                fd = torch.empty((recs.shape[0], self.full_words), dtype=torch.float32, device=self.lane_device)
+                rd = recs.to(self.lane_device)
+                torch.cuda.synchronize(self.lane_device)
+                self._lane(c)[0].expand(rd, fd)
+                torch.cuda.synchronize(self.lane_device)
+                full.copy_(fd)
             else:
                 self._lane(c)[0].expand(recs, full)
             recs = full
         if self._solve_fn is not None:
             self._solve_fn(recs, forces, status)
+        elif self.lane_device is not None:
+            self._solve_staged(self._lane(c)[0], recs, forces, status)
         else:
             self._lane(c)[0].solve(recs, forces, status)
+
+    def _solve_staged(self, lane, recs, forces, status):
+        """The rows to the lanes' GPU, the solve on the lane's handle, forces and status back."""
+        dev = self.lane_device
+        rd = recs.to(dev)
+        fd = torch.empty((rd.shape[0], self.cols), dtype=torch.float32, device=dev)
+        sd = torch.empty(rd.shape[0], dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize(dev)   # the copies run on torch's stream, the solve on the handle's
+        lane.solve(rd, fd, sd)
+        torch.cuda.synchronize(dev)
+        forces.copy_(fd)
+        status.copy_(sd)
 
     def _fork(self):
         """Every lane stream waits for the caller's stream (inputs ready, earlier work done)."""

@@ -94,6 +94,30 @@ class CmpcParams(ctypes.Structure):
     ]
 
 
+class CmpcModel(ctypes.Structure):
+    """ctypes mirror of ``cmpc_model`` (include/cmpc_solver.h): the robot's single rigid body."""
+
+    _fields_ = [("mass", ctypes.c_double), ("inertia", ctypes.c_double * 3)]
+
+
+# RobotState.h:25-26 (the A1): m = 12, I_body = diag(.07, .26, .242)
+DEFAULT_MASS = 12.0
+DEFAULT_INERTIA = (0.07, 0.26, 0.242)
+
+
+def make_model(mass: float = DEFAULT_MASS, inertia=DEFAULT_INERTIA) -> CmpcModel:
+    """A robot model: ``mass`` (kg) and the principal body-frame moments ``inertia`` = (Ixx, Iyy,
+    Izz) (kg m^2). The defaults are the reference's literals."""
+    inertia = tuple(float(x) for x in inertia)
+    if len(inertia) != 3:
+        raise ValueError("inertia takes the three principal moments (Ixx, Iyy, Izz)")
+    m = CmpcModel()
+    m.mass = float(mass)
+    for i, x in enumerate(inertia):
+        m.inertia[i] = x
+    return m
+
+
 # ConvexMPCLocomotion.cpp:617 (Q), :623 (alpha), :807 (mu = 0.4, f_max = 120); dtMPC = 0.002 * 13
 DEFAULT_WEIGHTS = (0.25, 0.25, 10, 10, 2, 50, 0, 0, 0.3, 0.2, 0.2, 0.1)
 

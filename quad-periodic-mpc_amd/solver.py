@@ -19,7 +19,7 @@ import os
 
 import numpy as np
 
-from .records import CmpcParams, LocoParams, make_params, record_words
+from .records import CmpcModel, CmpcParams, LocoParams, make_model, make_params, record_words
 from .records import (CERT_COST, CERT_COST0, CERT_GAP, CERT_VIOL, CERT_SWING, CERT_GRADMAX,  # noqa: F401
                       CERT_WORDS, MAX_HORIZON)
 
@@ -39,6 +39,7 @@ EXPORTED_SYMBOLS = (
     "cmpc_batch_assemble", "cmpc_batch_rollout", "cmpc_batch_admm", "cmpc_batch_expand",
     "cmpc_batch_evaluate", "cmpc_batch_evaluate_host", "cmpc_evaluate_last",
     "cmpc_batch_solve_due", "cmpc_batch_estimate_due",
+    "cmpc_batch_set_model", "cmpc_batch_get_model", "cmpc_set_model",
     "cmpc_batch_quadprog",   # include/cmpc_quadprog.h
 )
 
@@ -132,6 +133,10 @@ def load_library(path: str = LIB_PATH):
                                             ctypes.c_void_p, ctypes.c_void_p]
         lib.cmpc_batch_evaluate_host.argtypes = [ctypes.c_void_p, _fp, _fp, ctypes.c_int, _fp, _dp]
         lib.cmpc_evaluate_last.argtypes = [_fp, _dp]
+    if hasattr(lib, "cmpc_batch_set_model"):  # (A/B libraries built before the model was a parameter lack it)
+        lib.cmpc_batch_set_model.argtypes = [ctypes.c_void_p, ctypes.POINTER(CmpcModel)]
+        lib.cmpc_batch_get_model.argtypes = [ctypes.c_void_p, ctypes.POINTER(CmpcModel)]
+        lib.cmpc_set_model.argtypes = [ctypes.POINTER(CmpcModel)]
     lib.cmpc_batch_quadprog.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int] + \
         [ctypes.c_void_p] * 7 + [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int]
     _lib = lib
@@ -189,6 +194,15 @@ def update_problem_data(p, v, q, w, r, yaw, weights, state_trajectory, alpha, ga
         traj.ctypes.data_as(_dp), float(alpha), g.ctypes.data_as(_ip))
 
 
+def set_model(model: CmpcModel | None) -> None:
+    """``cmpc_set_model``: the robot model of the single-instance surface from the next
+    ``update_problem_data*`` call on (``None``: the default, m = 12, I = diag(.07, .26, .242))."""
+    lib = load_library()
+    if not hasattr(lib, "cmpc_set_model"):
+        raise CmpcError("this libcmpc_hip.so has no cmpc_set_model")
+    _check(lib.cmpc_set_model(ctypes.byref(model) if model is not None else None), "cmpc_set_model")
+
+
 def get_solution(index: int) -> float:
     return load_library().get_solution(int(index))
 
@@ -244,7 +258,7 @@ class BatchSolver:
     """Reentrant batched solver bound to one HIP stream (``cmpc_batch_*``)."""
 
     def __init__(self, params: CmpcParams | None = None, max_batch: int = 65536, stream=None,
-                 horizon: int = 10):
+                 horizon: int = 10, model: CmpcModel | None = None):
         self.lib = load_library()
         self.params = params if params is not None else make_params(horizon)
         self.max_batch = int(max_batch)
@@ -261,6 +275,30 @@ class BatchSolver:
         _check(self.lib.cmpc_batch_create(ctypes.byref(h), ctypes.byref(self.params),
                                           self.max_batch, s), "cmpc_batch_create")
         self._h = h
+        if model is not None:
+            try:
+                self.set_model(model)
+            except Exception:
+                self.close()
+                raise
+
+    def set_model(self, model: CmpcModel | None) -> None:
+        """The handle's robot model (``cmpc_batch_set_model``; ``None``: the default). Handle state
+        of its own: it survives :meth:`set_params` and applies to every call made after it. A
+        non-finite or non-positive field raises and leaves the handle's model as it was."""
+        if not hasattr(self.lib, "cmpc_batch_set_model"):
+            raise CmpcError("this libcmpc_hip.so has no cmpc_batch_set_model")
+        _check(self.lib.cmpc_batch_set_model(self._h, ctypes.byref(model) if model is not None else None),
+               "cmpc_batch_set_model")
+
+    @property
+    def model(self) -> CmpcModel:
+        """The handle's robot model as the library holds it (``cmpc_batch_get_model``)."""
+        if not hasattr(self.lib, "cmpc_batch_get_model"):
+            return make_model()
+        m = CmpcModel()
+        _check(self.lib.cmpc_batch_get_model(self._h, ctypes.byref(m)), "cmpc_batch_get_model")
+        return m
 
     @property
     def horizon(self) -> int:
