@@ -133,11 +133,24 @@ def build_tools(lib: str = LIB) -> str:
     the way the be2r controller links it (only include/cmpc_solver.h)."""
     exe = os.path.join(PKG, "cmpc_abi_latency")
     src = os.path.join(CSRC, "tools", "cmpc_abi_latency.cpp")
-    if not _stale(exe, [src, lib]):
-        return exe
-    subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe + ".tmp", src, f"-L{PKG}", "-lcmpc_hip",
-                    f"-Wl,-rpath,$ORIGIN", f"-Wl,-rpath,{PKG}"], check=True)
-    os.replace(exe + ".tmp", exe)
+    if _stale(exe, [src, lib]):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-o", exe + ".tmp", src, f"-L{PKG}", "-lcmpc_hip",
+                        f"-Wl,-rpath,$ORIGIN", f"-Wl,-rpath,{PKG}"], check=True)
+        os.replace(exe + ".tmp", exe)
+    build_mfma_probe()
+    return exe
+
+
+def build_mfma_probe() -> str:
+    """cmpc_mfma_probe: a stand-alone one-wave check of the broadcast 4x4x1 MFMA's register layout
+    and rounding, which the class-1 row sweeps (CMPC_C1_MFMA) rely on."""
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    exe = os.path.join(PKG, "cmpc_mfma_probe")
+    src = os.path.join(CSRC, "tools", "cmpc_mfma_probe.cpp")
+    if _stale(exe, [src]):
+        subprocess.run([hipcc, "-x", "hip", "--offload-arch=" + ARCH, "-O2", "-std=c++17", "-o",
+                        exe + ".tmp", src], check=True)
+        os.replace(exe + ".tmp", exe)
     return exe
 
 

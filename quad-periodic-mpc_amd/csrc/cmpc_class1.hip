@@ -14,7 +14,9 @@
 //   * LDS holds one packed 64x64 upper-row matrix (8.5 KB): H during assembly, then the raw
 //     Cholesky columns. Because the trailing matrix of a right-looking Cholesky stays
 //     symmetric, pivot column k is "register slot[k] of every lane": ONE ds_write_b32 per step
-//     publishes it, and the broadcast reads are ds_read_b128;
+//     publishes it, and the broadcast reads are ds_read_b128; the Cholesky's trailing sweep and
+//     the active set's reflection take the broadcast from lane c's register instead, as 4x4x1
+//     MFMA outer products with the A-operand broadcast (CMPC_C1_MFMA);
 //   * J = L^-T is solved left-looking inside the factorisation's pair steps: the stored columns
 //     are -L's, lane v keeps x_j = J[v][j] in the registers of the finished H columns, and each
 //     step adds the row sums over the finished columns (16-B broadcasts, four rows per read);
@@ -81,6 +83,24 @@
 // +0.9 %, 32768 -0.4 / +1.4 % (profiles/r06_s12/lib_ab.log)
 #ifndef CMPC_C1_XUNC
 #define CMPC_C1_XUNC 1
+#endif
+// Row sweeps as broadcast outer products on the matrix pipe (v_mfma_f32_4x4x1_16b_f32, cbsz 4):
+// every sweep FMA is slot[c] += (this lane's coefficient) x (a value lane c holds), and with
+// A = the lane-natural column register, B = the coefficient and abid = c / 4 one MFMA does
+//   slot[c + i] (lane v) += A(lane c + i) B(lane v),  i = 0..3,
+// a whole sweep chunk with no LDS broadcast and no VALU FMA (layout and rounding checked by
+// tools/cmpc_mfma_probe.cpp). MFMAs ignore EXEC: each sits in wave-uniform control flow.
+// The MFMA rounds as one fmaf, denormals included, and every stage keeps each element's order
+// of additions, so all of them give the LDS form's forces bit for bit.
+// 1: the Cholesky's rank-2 trailing sweep (config 3 +2.6 % over 0); 2: also the active set's
+// reflection update (0 to +1.1 % over 1 per rotation, separated in two sessions of three); 3:
+// also the fused J's row sums (does not separate from 2); 0: the LDS-broadcast FMAs
+// (profiles/r12_mfma)
+#ifndef CMPC_C1_MFMA
+#define CMPC_C1_MFMA 2
+#endif
+#if CMPC_C1_MFMA && !(CMPC_C1_CHOL2 && CMPC_C1_FUSEDJ)
+#error "CMPC_C1_MFMA needs the pair-step Cholesky with the fused J (CMPC_C1_CHOL2, CMPC_C1_FUSEDJ)"
 #endif
 
 // Phase profiler (diagnostic builds only, -DCMPC_PHASE_PROF): lane 0 of every solved instance
@@ -203,6 +223,22 @@ __device__ __forceinline__ void lsync() {
 }
 
 __device__ __forceinline__ float fdiv(float a, float b) { return a * fast_rcp(b); }
+
+#if CMPC_C1_MFMA
+typedef float f4m __attribute__((ext_vector_type(4)));
+// one sweep chunk: x_i (this lane) += col(lane C + i) * coef (this lane), i = 0..3 (C = 0 mod 4)
+template <int C>
+__device__ __forceinline__ void mfma_chunk(float col, float coef, float& x0, float& x1, float& x2,
+                                           float& x3) {
+  static_assert((C & 3) == 0 && C >= 0 && C < 64, "chunk start");
+  f4m acc = {x0, x1, x2, x3};
+  acc = __builtin_amdgcn_mfma_f32_4x4x1f32(col, coef, acc, 4, C / 4, 0);
+  x0 = acc[0];
+  x1 = acc[1];
+  x2 = acc[2];
+  x3 = acc[3];
+}
+#endif
 
 // Register pin: forces every row element to be materialised at this point. Without it LLVM sinks
 // the right-looking updates of slot[c] down to the step that first reads slot[c] (turning the
@@ -410,6 +446,10 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
   // stored columns (raw even, corrected odd) are what J = L^-T needs. Odd n: the last step's
   // second pivot is the identity padding row (H[n][n] = 1, no coupling).
   float i0n = 1.f, betan = 0.f, i1n = 1.f, g0n = 0.f, g1n = 0.f;
+#if CMPC_C1_MFMA
+  // the two published columns as look leaves them, one element per lane: the MFMA sweep's A operand
+  float pub0n = 0.f, pub1n = 0.f;
+#endif
   // pivot data of the step at columns (j, j+1) from the current rows, and the publish of both
   // columns (lanes >= the columns' chunk start)
   auto look = [&](auto JJ) {
@@ -432,13 +472,24 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
     // corrected column j+1 likewise), so the sweep and the left-looking J both read them as they are
     g0n = -g0n * i0n;
     g1n = -g1n * i1n;
+#if CMPC_C1_MFMA
+    // the sweep takes the columns from these registers; the stores feed only the J sums, which
+    // order themselves after them (lsync ahead of the sums)
+    pub0n = (v >= j) ? -slot[j] * i0n : 0.f;
+    pub1n = (v >= j1) ? -s1 * i1n : 0.f;
+    if (v >= cj && v < NV) sh.P[G::prow(j) + v - cj] = pub0n;
+    if (v >= cj1 && v < NV) sh.P[G::prow(j1) + v - cj1] = pub1n;
+#else
     if (v >= cj && v < NV) sh.P[G::prow(j) + v - cj] = (v >= j) ? -slot[j] * i0n : 0.f;
     if (v >= cj1 && v < NV) sh.P[G::prow(j1) + v - cj1] = (v >= j1) ? -s1 * i1n : 0.f;
+#endif
 #else
     if (v >= cj && v < NV) sh.P[G::prow(j) + v - cj] = (v >= j) ? slot[j] : 0.f;
     if (v >= cj1 && v < NV) sh.P[G::prow(j1) + v - cj1] = (v >= j1) ? s1 : 0.f;
 #endif
+#if !CMPC_C1_MFMA
     lsync();
+#endif
     }
   };
   if (n > 0) look(std::integral_constant<int, 0>{});
@@ -472,6 +523,29 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       const float a1 = (v > k1) ? -s1 * (i1 * i1) : 0.f;
 #endif
       slot[NV] = fmaf(a1, g1, fmaf(a0, g0, slot[NV]));
+#if CMPC_C1_MFMA
+      // slot[c] += a0 P'_k[c] + a1 P'_k+1[c] with P'[c] taken from lane c's register. The chunk
+      // with columns k+2, k+3 takes both pivots first (the look-ahead follows it); the others
+      // all of pivot k, then all of pivot k+1, so that two MFMAs on one accumulator sit a
+      // sweep apart. Each element still gets pivot k's FMA before pivot k+1's, as above.
+      if constexpr (c2 < NV) {
+        const float p0 = pub0n, p1 = pub1n;
+        mfma_chunk<c2>(p0, a0, slot[c2 + 0], slot[c2 + 1], slot[c2 + 2], slot[c2 + 3]);
+        mfma_chunk<c2>(p1, a1, slot[c2 + 0], slot[c2 + 1], slot[c2 + 2], slot[c2 + 3]);
+        if constexpr (k2 < NV) {
+          if (k2 < n) look(std::integral_constant<int, k2>{});  // columns k+2, k+3 are final
+        }
+        static_for<c2 / 4 + 1, NV / 4>([&](auto JC) {
+          constexpr int c = 4 * decltype(JC)::value;
+          mfma_chunk<c>(p0, a0, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
+        });
+        static_for<c2 / 4 + 1, NV / 4>([&](auto JC) {
+          constexpr int c = 4 * decltype(JC)::value;
+          mfma_chunk<c>(p1, a1, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
+        });
+      }
+      lsync();  // the J sums below read the stored columns
+#else
       static_for<c2 / 4, NV / 4>([&](auto JC) {
         constexpr int c = 4 * decltype(JC)::value;
         const float4 r0 = *reinterpret_cast<const float4*>(&sh.P[rk + c - c0]);
@@ -483,6 +557,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
         }
         CMPC_SWEEP_FENCE(c);
       });
+#endif
 #if CMPC_C1_FUSEDJ == 2
       // J = L^-T, left-looking, four rows per 16-B read: at k = 0 mod 4 the sums of rows k..k+3
       // over every finished column j < k (one ds_read_b128 broadcast of P'_j[k..k+3] per column,
@@ -493,6 +568,34 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       if constexpr ((k & 3) == 0) {
         f2v t0 = {(v == k) ? 1.f : 0.f, 0.f}, t1 = {(v == k1) ? 1.f : 0.f, 0.f};
         f2v t2 = {(v == k + 2) ? 1.f : 0.f, 0.f}, t3 = {(v == k + 3) ? 1.f : 0.f, 0.f};
+#if CMPC_C1_MFMA >= 3
+        // the same sums on the matrix pipe: per finished column q one lane-natural 4-B read of
+        // the stored column (lane c gets P'_q[c]; only lanes k..k+3 are selected, abid = k / 4)
+        // and one MFMA t_i += P'_q[k + i] x_q, i = 0..3, in place of a 16-B broadcast and four
+        // FMAs. Two accumulator tuples, even columns in one and odd in the other, as the .x / .y
+        // chains above: consecutive MFMAs do not chain and every sum keeps its order.
+        {
+          f4m te = {t0.x, t1.x, t2.x, t3.x}, to = {0.f, 0.f, 0.f, 0.f};
+          const int vc = (v < NV) ? v : NV - 1;  // (lanes without a row stay inside row q)
+          piped_sweep<0, k, 2>(
+              [&](auto C) {
+                constexpr int q = decltype(C)::value;  // columns q .. q+3 (4 | k), rows from q & ~3 = q
+                return float4{sh.P[G::prow0(q) + vc], sh.P[G::prow0(q + 1) + vc],
+                              sh.P[G::prow0(q + 2) + vc], sh.P[G::prow0(q + 3) + vc]};
+              },
+              [&](auto C, float4 l) {
+                constexpr int q = decltype(C)::value;
+                te = __builtin_amdgcn_mfma_f32_4x4x1f32(l.x, slot[q], te, 4, k / 4, 0);
+                to = __builtin_amdgcn_mfma_f32_4x4x1f32(l.y, slot[q + 1], to, 4, k / 4, 0);
+                te = __builtin_amdgcn_mfma_f32_4x4x1f32(l.z, slot[q + 2], te, 4, k / 4, 0);
+                to = __builtin_amdgcn_mfma_f32_4x4x1f32(l.w, slot[q + 3], to, 4, k / 4, 0);
+              });
+          t0 = {te[0], to[0]};
+          t1 = {te[1], to[1]};
+          t2 = {te[2], to[2]};
+          t3 = {te[3], to[3]};
+        }
+#else
 #if CMPC_C1_JPIPE
         // loads of the next column group issued before this group's FMAs (one group ahead)
         piped_sweep<0, k, 1>(
@@ -528,6 +631,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
           __builtin_amdgcn_sched_barrier(0);
         });
 #endif
+#endif  // CMPC_C1_MFMA >= 3
         const float hk = sh.P[G::prow(k) + k1 - (k & ~3)];  // -L[k+1][k]
         const float xk = (t0.x + t0.y) * i0;
         slot[k] = xk;
@@ -869,6 +973,9 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       const bool add = !zero_step && t2 <= t1;
       const bool add_u = __builtin_amdgcn_readfirstlane((int)add) != 0;
       float beta = 0.f, sigma = 0.f;  // w = d2 + sigma e_q
+#if CMPC_C1_MFMA >= 2
+      float wreg = 0.f;  // w, one element per lane (0 on a drop): the reflection MFMAs' A operand
+#endif
       if (add) {
         // ---- add p: the Householder reflection I - beta w w' on columns q..n-1 maps
         // d[q..n-1] to -sgn(d_q) |d[q..n-1]| e_q; R gains the column (d[0..q-1], -sgn ts)
@@ -877,7 +984,11 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
         const float sgn = (dq >= 0.f) ? 1.f : -1.f;
         beta = fast_rcp(ts * (ts + fabsf(dq)));  // 2 / (w'w)
         sigma = sgn * ts;
+#if CMPC_C1_MFMA >= 2
+        wreg = (v == q) ? dq + sgn * ts : dm;
+#else
         sh.vbuf()[v] = (v == q) ? dq + sgn * ts : dm;
+#endif
         const int offq = rcol(q);
         if (v < q) sh.P[offq + v] = dv;
         if (v == q) {
@@ -901,7 +1012,9 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
         // ---- drop active constraint kk: shift positions kk+1..q-1 down, remove column kk of
         // R and re-triangularise rows kk..q-1 (lane c rebuilds column c of R in place: every
         // read of an old entry precedes, in this wavefront's LDS order, the write reusing it)
+#if CMPC_C1_MFMA < 2
         sh.vbuf()[v] = 0.f;
+#endif
         const int k = __builtin_amdgcn_readfirstlane(kk);
         const int ak = rli(act_reg, k);
         if (v == 0) sh.cmask[ak / 6] &= (unsigned char)~(1u << (ak % 6));
@@ -968,12 +1081,20 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
         // column pick (scalar branches on q) and one FMA instead of a second row-long dot product
         const int qs = __builtin_amdgcn_readfirstlane(q);
         const float bt = -beta * fmaf(sigma, pick_col<0, NV>(slot, qs), zv);
+#if CMPC_C1_MFMA >= 2
+        // J_v[c] += bt w[c] with w[c] from lane c's register: no store of w, no broadcast reads
+        static_for<0, NV / 4>([&](auto JC) {
+          constexpr int c = 4 * decltype(JC)::value;
+          mfma_chunk<c>(wreg, bt, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
+        });
+#else
         piped_sweep<0, NV, C1_PIPE_GRP>(
             [&](auto C) { return *reinterpret_cast<const float4*>(&sh.vbuf()[decltype(C)::value]); },
             [&](auto C, float4 w4) {
               constexpr int c = decltype(C)::value;
               axpy4(bt, w4, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
             });
+#endif
       }
       C1_SUB(4);
       if (!add_u) {

@@ -13,8 +13,11 @@ averaged over the profiled launches:
   lds_bank_conflict_frac = SQ_LDS_BANK_CONFLICT / SQ_ACTIVE_INST_LDS
   wait_frac / issue_stall_frac / active_frac = SQ_WAIT_ANY, SQ_WAIT_INST_ANY,
                           SQ_ACTIVE_INST_ANY over SQ_WAVE_CYCLES (disjoint, sum ~ 1)
+  mfma_insts_per_wave, mfma_busy_cycles_per_wave (pass sq3, where it was run)
 
 usage: python scripts/pmc_collect.py <tag>    (reads gpurun_out/<tag>/<case>/<pass>/)
+A second argument, a kernel substring (e.g. cmpc_solve_c1_kernel): profiles/pmc_summary.json keeps
+every recorded entry, and only the matching kernels of the profiled cases take the new figures.
 """
 from __future__ import annotations
 
@@ -57,6 +60,7 @@ def read(path):
 
 def main():
     tag = sys.argv[1]
+    only = sys.argv[2] if len(sys.argv) > 2 else None
     src = os.path.join(ROOT, "gpurun_out", tag)
     dst = os.path.join(ROOT, "profiles", tag)
     os.makedirs(dst, exist_ok=True)
@@ -67,7 +71,7 @@ def main():
             continue
         allv = {}
         meta = {}
-        for p in ("fetch", "write", "sq1", "sq2"):
+        for p in ("fetch", "write", "sq1", "sq2", "sq3"):
             v, m = read(os.path.join(cdir, p, "run_counter_collection.csv"))
             allv.update(v)
             meta.update(m)
@@ -86,12 +90,15 @@ def main():
                 d["fetch_kib_raw"], d["write_kib"] = fetch, write
             waves = avg("SQ_WAVES")
             for c in ("SQ_INSTS_VALU", "SQ_INSTS_LDS", "SQ_INSTS_SALU", "SQ_INSTS_SMEM",
-                      "SQ_INSTS_VMEM_RD", "SQ_INSTS_VMEM_WR"):
+                      "SQ_INSTS_VMEM_RD", "SQ_INSTS_VMEM_WR", "SQ_INSTS_MFMA"):
                 x = avg(c)
                 if x is not None and waves:
                     d[c.lower().replace("sq_insts_", "") + "_insts_per_wave"] = round(x / waves, 1)
             if waves:
                 d["waves"] = waves
+            mbusy = avg("SQ_VALU_MFMA_BUSY_CYCLES")
+            if mbusy is not None and waves:
+                d["mfma_busy_cycles_per_wave"] = round(mbusy / waves, 1)
             act_valu, gui = avg("SQ_ACTIVE_INST_VALU"), avg("GRBM_GUI_ACTIVE")
             if act_valu is not None and gui:
                 d["valu_busy"] = round(act_valu * 4 / (SIMDS * gui), 4)
@@ -113,9 +120,22 @@ def main():
                    note="per launch, averaged over the profiled launches (bench.py --steps 2 "
                         "--warmup 1); HBM bytes = 2 x FETCH_SIZE + WRITE_SIZE; valu_busy = "
                         "SQ_ACTIVE_INST_VALU x 4 / (1024 SIMDs x GRBM_GUI_ACTIVE)")
-    for path in (os.path.join(dst, "pmc_summary.json"), os.path.join(ROOT, "profiles", "pmc_summary.json")):
-        with open(path, "w") as f:
-            json.dump(summary, f, indent=1)
+    with open(os.path.join(dst, "pmc_summary.json"), "w") as f:
+        json.dump(summary, f, indent=1)
+    top = os.path.join(ROOT, "profiles", "pmc_summary.json")
+    if only:
+        # keep the recorded summary; only the named kernels' entries in the profiled cases take the
+        # new figures (a figure of a pass that was not run again, e.g. the HBM bytes, stays)
+        with open(top) as f:
+            old = json.load(f)
+        new_cases = {c["case"]: c["kernels"] for c in cases}
+        for oc in old["cases"]:
+            for k, d in new_cases.get(oc["case"], {}).items():
+                if only in k:
+                    oc["kernels"].setdefault(k, {}).update(d)
+        summary = old
+    with open(top, "w") as f:
+        json.dump(summary, f, indent=1)
     for c in cases:
         print(c["case"])
         for k, d in c["kernels"].items():
