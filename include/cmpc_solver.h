@@ -334,6 +334,12 @@ CMPC_EXTERNC int cmpc_set_model(const cmpc_model* m);
  * (row-major) and qg per instance, all variables kept (no swing elimination). */
 CMPC_EXTERNC int cmpc_batch_condense(cmpc_batch* h, const float* d_records, int batch,
                                      float* d_H, float* d_g);
+/* The same in row-owner mode: every row of qH carries its own recursion on down to step 0 and
+ * writes its entries on both sides of the diagonal, none mirrored from the row above, so qH is
+ * symmetric to fp32 rounding only. This is how the class-1 solver condenses tables with two
+ * stance feet at every step; qg as above. New API. */
+CMPC_EXTERNC int cmpc_batch_condense_rows(cmpc_batch* h, const float* d_records, int batch,
+                                          float* d_H, float* d_g);
 /* JCQP ADMM settings: update_solver_settings(max_iter, rho, sigma, solver_alpha, terminate, .)
  * (convexMPC_interface.cpp:109-129 -> QpProblemSettings, JCQP/QpProblem.h:15-28). */
 typedef struct cmpc_admm_settings {

@@ -519,7 +519,15 @@ extern "C" int cmpc_batch_read_timing(cmpc_batch* h, float* ms, int* steps_recor
 extern "C" int cmpc_batch_condense(cmpc_batch* h, const float* d_records, int batch, float* d_H,
                                    float* d_g) {
   if (!h || batch < 0 || batch > h->max_batch) return -1;
-  hipError_t e = cmpc::launch_condense(d_records, batch, h->kp, d_H, d_g, h->stream);
+  hipError_t e = cmpc::launch_condense(d_records, batch, h->kp, d_H, d_g, false, h->stream);
+  if (e != hipSuccess) return fail("launch_condense", e);
+  return 0;
+}
+
+extern "C" int cmpc_batch_condense_rows(cmpc_batch* h, const float* d_records, int batch, float* d_H,
+                                        float* d_g) {
+  if (!h || batch < 0 || batch > h->max_batch) return -1;
+  hipError_t e = cmpc::launch_condense(d_records, batch, h->kp, d_H, d_g, true, h->stream);
   if (e != hipSuccess) return fail("launch_condense", e);
   return 0;
 }

@@ -102,6 +102,14 @@
 #if CMPC_C1_MFMA && !(CMPC_C1_CHOL2 && CMPC_C1_FUSEDJ)
 #error "CMPC_C1_MFMA needs the pair-step Cholesky with the fused J (CMPC_C1_CHOL2, CMPC_C1_FUSEDJ)"
 #endif
+// Tables with exactly two stance feet at every step (trot, the deployed gait) and 6 N <= NV:
+// reduced column 6 i + 3 s + a of step i's s-th stance foot is a compile-time register index, so
+// lane v condenses its whole row (both sides of the diagonal, from its own chain continued below
+// step k_v) straight into slot[], with no H exchange through the LDS and no row load
+// (DESIGN.md §4.1 round 13). 0: every table takes the exchange.
+#ifndef CMPC_C1_STATIC2
+#define CMPC_C1_STATIC2 1
+#endif
 
 // Phase profiler (diagnostic builds only, -DCMPC_PHASE_PROF): lane 0 of every solved instance
 // adds the s_memtime cycles spent in each stage to g_c1_phase (scripts/phase_prof.py).
@@ -250,6 +258,25 @@ __device__ __forceinline__ void pin(float (&x)[M]) {
   for (int c = 0; c < M; c++) asm volatile("" : "+v"(x[c]));
 }
 
+// the same for the elements [C0, C1) alone
+template <int C0, int C1, int M>
+__device__ __forceinline__ void pin_range(float (&x)[M]) {
+  static_assert(0 <= C0 && C0 <= C1 && C1 <= M, "element range");
+#pragma unroll
+  for (int c = C0; c < C1; c++) asm volatile("" : "+v"(x[c]));
+}
+
+// A value at a wave-uniform address of read-only global memory re-read where it is used, as
+// karg_late does for the argument segment: a scalar load behind a pointer the optimiser cannot
+// see through, so the value holds SGPRs only around its use
+template <typename T>
+__device__ __forceinline__ T cmem_late(const void* base, int off) {
+  typedef const __attribute__((address_space(4))) char* cptr;
+  cptr p = (cptr)(uintptr_t)base;
+  asm volatile("" : "+s"(p));
+  return *reinterpret_cast<const __attribute__((address_space(4))) T*>(p + off);
+}
+
 // Element q (LO <= q < HI, wave-uniform: an SGPR) of a register-resident row, as a tree of scalar
 // branches on q with one v_mov at its leaf: no LDS traffic and almost no VALU. The opaque leaf keeps
 // the optimiser from folding the branches into v_cndmask selects (HI - LO - 1 of them: measured
@@ -279,7 +306,11 @@ __device__ __forceinline__ float pick_col(const float (&x)[MA], int q) {
     if (((c) & (CMPC_FENCE_COLS - 1)) == CMPC_FENCE_COLS - 4) __builtin_amdgcn_sched_barrier(0); \
   } while (0)
 
-template <int NV>
+// POFF, OOFF (CMPC_C1_STATIC2): the byte offsets of the kernel's KParams and of its three output
+// pointers (forces, status, iters, one after the other) in its argument segment. The outputs are
+// then read where the instance is written out (karg_late), not held in six SGPRs from kernel
+// entry, and fout / st_out / it_out are not used.
+template <int NV, int POFF = -1, int OOFF = -1>
 __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KParams& P,
                                          SharedC1<NV>& sh, float* __restrict__ fout,
                                          uint8_t* __restrict__ st_out, int32_t* __restrict__ it_out,
@@ -371,6 +402,17 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
   // ---- condensation: lane v builds H[v][w] for w >= v into packed P, and its gradient g_v
   const bool real = v < n;
   float gv;
+#if CMPC_C1_STATIC2
+  float slot[NV + 1];
+  // two stance feet at every step and every step inside the row: then n = 6 N, k_v = v / 6 and
+  // the column of entry (i, s, a) is 6 i + 3 s + a. From the stance ballots alone (wave-uniform,
+  // the record's property: the same path in every batch and launch form)
+  bool st2 = 6 * N <= NV;
+  static_for<0, NV / 6>([&](auto IC) {
+    constexpr int i = decltype(IC)::value;
+    if (i < N) st2 = st2 && (__builtin_popcount(step_mask(msk0, msk1, i)) == 2);
+  });
+#endif
   {
     const int kv = real ? sh.varblk[v] : 0;
     const int cv = real ? sh.varcol[v] : 0;
@@ -383,34 +425,118 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
     gv = grad_from_moments(b, u1, u2, &sh.P[OFF_E + 16 * kv], &sh.P[OFF_ZE + 16 * kv]);
     gv = real ? gv : 0.f;
     lsync();  // every moment read is issued before P is overwritten
-    const int myrow = G::tri(v);
     float z[13];
 #pragma unroll
     for (int j = 0; j < 13; j++) z[j] = 0.f;
-    for (int i = N - 1; i >= 0; i--) {
-      // z_i = S Adt^{i-kv} b_v + Adt' z_{i+1}  (the S term only for i >= kv)
-      const bool act = real && (i >= kv);
-      const float k = (float)(i - kv);
-      const float k2 = 0.5f * k * (k - 1.f);
-      float gk[13];
-      col_power(b, u1, u2, k, k2, gk);
+#if CMPC_C1_STATIC2
+    if (st2) {
+      // the model's uniform values in SGPRs for the unrolled steps: the row is live beside them
+      Model ms;
 #pragma unroll
-      for (int j = 0; j < 13; j++) gk[j] = act ? gk[j] : 0.f;
-      recur(md, wts, gk, z);
-      asm volatile("" ::: "memory");  // the step's LDS traffic stays inside the step
-      const int wb = __builtin_amdgcn_readfirstlane(sh.blkbase[i]);
-      step_entries(md, cg, sh.u.BdtT, step_mask(msk0, msk1, i), wb, z, [&](int w, float val) {
-        if (w == v) val += P.alpha2;  // qH = 2 (B'SB + alpha I), SolverMPC.cpp:806
-        if (act && w >= v) sh.P[myrow + w] = val;
+      for (int j = 0; j < 9; j++) { ms.R[j] = rfl(md.R[j]); ms.n1r[j] = rfl(md.n1r[j]); }
+      ms.dt = rfl(md.dt); ms.dth = rfl(md.dth); ms.xdrag = rfl(md.xdrag); ms.im = rfl(md.im);
+#pragma unroll
+      for (int j = 0; j < 3; j++) ms.ib[j] = md.ib[j];
+      static_for<0, NV / 6>([&](auto IC) {
+        constexpr int i = NV / 6 - 1 - decltype(IC)::value;
+        if (i < N) {
+          // the same chain as below; at i < kv it goes on as z_i = Adt' z_{i+1}, and
+          // 2 b_w' z_i is then H[v][w] of the lower triangle (k_w = i < k_v)
+          const bool act = real && (i >= kv);
+          const float k = (float)(i - kv);
+          const float k2 = 0.5f * k * (k - 1.f);
+          float gk[13];
+          col_power(b, u1, u2, k, k2, gk);
+#pragma unroll
+          for (int j = 0; j < 13; j++) gk[j] = act ? gk[j] : 0.f;
+          {
+            // the weights re-read from the argument segment (scalar loads) in every step: held
+            // from kernel entry they keep twelve SGPRs through the whole stage, which spills
+            const kf32x4 w0 = karg_late<kf32x4>(POFF + (int)offsetof(KParams, wts)),
+                         w1 = karg_late<kf32x4>(POFF + (int)offsetof(KParams, wts) + 16),
+                         w2 = karg_late<kf32x4>(POFF + (int)offsetof(KParams, wts) + 32);
+            const float ws[13] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, 0.f};
+            recur(ms, ws, gk, z);
+          }
+          StepProj pj;
+          step_proj(ms, cg, z, pj);
+          // (the ballot opaque: the step's nibble is shifted out here, not kept from the test above)
+          unsigned long long mo0 = msk0;
+          asm volatile("" : "+s"(mo0));
+          const unsigned mi = step_mask(mo0, 0ull, i);  // (i < 16: the first ballot alone)
+          // the foot positions likewise, from the record in global memory (the values of cg.r)
+          const kf32x4 p0 = cmem_late<kf32x4>(rec, 4 * CMPC_REC_R), p1 = cmem_late<kf32x4>(rec, 4 * CMPC_REC_R + 16),
+                       p2 = cmem_late<kf32x4>(rec, 4 * CMPC_REC_R + 32);
+          const float rs[12] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w, p2.x, p2.y, p2.z, p2.w};
+          static_for<0, 2>([&](auto SC) {
+            constexpr int s = decltype(SC)::value;
+            // the step's s-th stance foot: lowest / next set bit of the nibble, its position
+            // selected among the twelve uniform values
+            const int f = __builtin_ctz(s == 0 ? mi : (mi & (mi - 1u)));
+            // (through sopq: a select between the array's elements as they stand becomes a select
+            // of their addresses, and the array goes to scratch)
+            const auto foot = [&](int j) {
+              const float a0 = sopq(rs[j]), a1 = sopq(rs[j + 1]), a2 = sopq(rs[j + 2]), a3 = sopq(rs[j + 3]);
+              return (f & 2) ? ((f & 1) ? a3 : a2) : ((f & 1) ? a1 : a0);
+            };
+            const float r0 = foot(0), r1 = foot(4), r2 = foot(8);
+            float val[3];
+            foot_entries(pj, r0, r1, r2, val);
+            static_for<0, 3>([&](auto AC) {
+              constexpr int c = 6 * i + 3 * s + decltype(AC)::value;
+              float x = val[decltype(AC)::value];
+              if (c == v) x += P.alpha2;  // qH = 2 (B'SB + alpha I), SolverMPC.cpp:806
+              slot[c] = real ? x : ((c == v) ? 1.f : 0.f);
+            });
+          });
+        } else {
+          static_for<6 * i, 6 * i + 6>([&](auto C) {
+            constexpr int c = decltype(C)::value;
+            slot[c] = (c == v) ? 1.f : 0.f;
+          });
+        }
+        // the step's entries are formed here: nothing of the chain sinks past it
+        pin_range<6 * i, 6 * i + 6>(slot);
       });
+      static_for<6 * (NV / 6), NV>([&](auto C) {  // identity padding past the last whole step
+        constexpr int c = decltype(C)::value;
+        slot[c] = (c == v) ? 1.f : 0.f;
+      });
+      slot[NV] = gv;
+      C1_MARK(1);
+    } else
+#endif
+    {
+      const int myrow = G::tri(v);
+      for (int i = N - 1; i >= 0; i--) {
+        // z_i = S Adt^{i-kv} b_v + Adt' z_{i+1}  (the S term only for i >= kv)
+        const bool act = real && (i >= kv);
+        const float k = (float)(i - kv);
+        const float k2 = 0.5f * k * (k - 1.f);
+        float gk[13];
+        col_power(b, u1, u2, k, k2, gk);
+#pragma unroll
+        for (int j = 0; j < 13; j++) gk[j] = act ? gk[j] : 0.f;
+        recur(md, wts, gk, z);
+        asm volatile("" ::: "memory");  // the step's LDS traffic stays inside the step
+        const int wb = __builtin_amdgcn_readfirstlane(sh.blkbase[i]);
+        step_entries(md, cg, sh.u.BdtT, step_mask(msk0, msk1, i), wb, z, [&](int w, float val) {
+          if (w == v) val += P.alpha2;  // qH = 2 (B'SB + alpha I), SolverMPC.cpp:806
+          if (act && w >= v) sh.P[myrow + w] = val;
+        });
+      }
+      lsync();
     }
   }
-  lsync();
-  C1_MARK(1);
 
   // ---- row v of H into registers (full symmetric; identity padding for v >= n) ----------
+#if CMPC_C1_STATIC2
+  if (!st2)  // (the two-stance rows are in slot[] already)
+#else
   float slot[NV + 1];
+#endif
   {
+    C1_MARK(1);
     const int vv = (v < NV) ? v : 0;  // lanes without a row read row 0 (and keep a zero row)
     const int myrow = G::tri(vv);
     static_for<0, NV>([&](auto C) {
@@ -421,8 +547,8 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       if ((c & 7) == 7) __builtin_amdgcn_sched_barrier(0);
     });
     slot[NV] = gv;
+    lsync();
   }
-  lsync();
 
   // ---- bordered Cholesky [H | g]: raw column k = slot[k] of every lane -> P row k ----------
   // Look-ahead: step k publishes column k+1 (and takes its pivot d_{k+1} and border g_{k+1})
@@ -1125,6 +1251,12 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
   C1_MARK(4);
   // ---- scatter (q_soln layout 12 k + 3 leg + axis, swing -> 0) staged in LDS, coalesced out
   const bool ok = (status == CMPC_OK);
+  if constexpr (OOFF >= 0) {
+    fout = karg_late<float*>(OOFF) + (size_t)inst * P.out_cols;
+    st_out = karg_late<uint8_t*>(OOFF + 8) + inst;
+    int32_t* const it_all = karg_late<int32_t*>(OOFF + 16);
+    it_out = it_all ? it_all + inst : nullptr;
+  }
   for (int t = v; t < 12 * N; t += 64) sh.P[t] = 0.f;
   lsync();
   if (ok && v < n) sh.P[12 * sh.varblk[v] + sh.varcol[v]] = xv;
@@ -1168,8 +1300,22 @@ __global__ __launch_bounds__(64, NV == 60 ? CMPC_W1_WAVES_60 : CMPC_W1_WAVES_PER
   const unsigned hw_id = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID
   const unsigned xcc_id = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // HW_REG_XCC_ID
 #endif
+#if CMPC_C1_STATIC2
+  using KP = KArg<2, decltype(&cmpc_solve_c1_kernel<NV>)>;  // the KParams argument, located by this signature
+  static_assert(std::is_same<typename KP::type, KParams>::value, "argument 2 is the KParams");
+  using K = decltype(&cmpc_solve_c1_kernel<NV>);
+  static_assert(std::is_same<typename KArg<3, K>::type, float*>::value &&
+                    std::is_same<typename KArg<4, K>::type, uint8_t*>::value &&
+                    std::is_same<typename KArg<5, K>::type, int32_t*>::value &&
+                    KArg<4, K>::offset() == KArg<3, K>::offset() + 8 &&
+                    KArg<5, K>::offset() == KArg<3, K>::offset() + 16,
+                "arguments 3..5 are forces, status, iters");
+  solve_c1<NV, KP::offset(), KArg<3, K>::offset()>(recs + (size_t)t * P.rec_words, P, sh, nullptr, nullptr,
+                                                   nullptr, ovf_list, ovf_count, t);
+#else
   solve_c1<NV>(recs + (size_t)t * P.rec_words, P, sh, forces + (size_t)t * P.out_cols, status + t,
                iters ? iters + t : nullptr, ovf_list, ovf_count, t);
+#endif
 #ifdef CMPC_PLACE_PROF
   const unsigned long long t_end = wall_clock64();
   if (threadIdx.x == 0 && t < kPlaceMax) {

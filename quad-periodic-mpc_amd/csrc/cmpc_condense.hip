@@ -4,6 +4,10 @@
 // structured recursions as the solver kernels (cmpc_common.h) — never forming A_qp, B_qp or the
 // dense 13N x 13N weight matrix S. One 256-thread workgroup per instance, grid-strided; the
 // symmetric H is written straight to the caller's buffer.
+// Row-owner mode (rows): every row runs its chain on down to step 0 (below its own step k_v as
+// z_i = Adt' z_{i+1}, the source term masked off) and writes its own entries on both sides of the
+// diagonal, nothing mirrored: what class 1's two-stance rows compute (cmpc_class1.hip,
+// CMPC_C1_STATIC2), here under the fp64 check of the parity hook.
 #include "cmpc_common.h"
 
 namespace cmpc {
@@ -20,7 +24,7 @@ struct SharedC {
 
 // One instance: H [n x n] row-major (n = 12 N) and g [n] of rec.
 __device__ void condense_one(const float* __restrict__ rec, const KParams& P, SharedC& sh,
-                             float* __restrict__ H, float* __restrict__ g) {
+                             float* __restrict__ H, float* __restrict__ g, bool rows) {
   const int tid = threadIdx.x;
   const int N = P.N;
   const int n = 12 * N;
@@ -58,11 +62,14 @@ __device__ void condense_one(const float* __restrict__ rec, const KParams& P, Sh
     float z[13];
 #pragma unroll
     for (int j = 0; j < 13; j++) z[j] = 0.f;
-    for (int i = N - 1; i >= kv; i--) {
+    for (int i = N - 1; i >= (rows ? 0 : kv); i--) {
+      const bool act = i >= kv;  // (the solvers' mask: below step kv the chain has no source term)
       const float k = (float)(i - kv);
       const float k2 = 0.5f * k * (k - 1.f);
       float gk[13];
       col_power(b, u1, u2, k, k2, gk);
+#pragma unroll
+      for (int j = 0; j < 13; j++) gk[j] = act ? gk[j] : 0.f;
       recur(md, wts, gk, z);
       // every foot-step is kept: all four feet, columns 12 i .. 12 i + 11 (the solvers' entry form)
       step_entries(md, cg, sh.BdtT, 15u, 12 * i, z, [&](int w, float val) {
@@ -70,7 +77,9 @@ __device__ void condense_one(const float* __restrict__ rec, const KParams& P, Sh
 #ifdef CMPC_DIAG_PERTURB  // diagnostic builds only: a deliberately wrong qH (shows the parity gate fails)
         val *= 1.f + CMPC_DIAG_PERTURB;
 #endif
-        if (w >= v) {
+        if (rows) {
+          H[(size_t)v * n + w] = val;
+        } else if (w >= v) {
           H[(size_t)v * n + w] = val;
           H[(size_t)w * n + v] = val;
         }
@@ -80,11 +89,12 @@ __device__ void condense_one(const float* __restrict__ rec, const KParams& P, Sh
 }
 
 __global__ __launch_bounds__(NTG) void cmpc_condense_kernel(const float* __restrict__ recs, int batch, KParams P,
-                                                            float* __restrict__ Hout, float* __restrict__ gout) {
+                                                            float* __restrict__ Hout, float* __restrict__ gout,
+                                                            int rows) {
   __shared__ SharedC sh;
   const size_t n = 12 * (size_t)P.N;
   for (int inst = blockIdx.x; inst < batch; inst += gridDim.x) {
-    condense_one(recs + (size_t)inst * P.rec_words, P, sh, Hout + inst * n * n, gout + inst * n);
+    condense_one(recs + (size_t)inst * P.rec_words, P, sh, Hout + inst * n * n, gout + inst * n, rows != 0);
     __syncthreads();
   }
 }
@@ -92,10 +102,11 @@ __global__ __launch_bounds__(NTG) void cmpc_condense_kernel(const float* __restr
 }  // namespace
 
 hipError_t launch_condense(const float* d_recs, int batch, const KParams& P, float* d_H, float* d_g,
-                           hipStream_t stream) {
+                           bool rows, hipStream_t stream) {
   if (batch <= 0) return hipSuccess;
   const int grid = batch < 2048 ? batch : 2048;
-  hipLaunchKernelGGL(cmpc_condense_kernel, dim3(grid), dim3(NTG), 0, stream, d_recs, batch, P, d_H, d_g);
+  hipLaunchKernelGGL(cmpc_condense_kernel, dim3(grid), dim3(NTG), 0, stream, d_recs, batch, P, d_H, d_g,
+                     rows ? 1 : 0);
   return hipGetLastError();
 }
 

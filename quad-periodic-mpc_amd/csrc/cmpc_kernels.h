@@ -186,7 +186,7 @@ hipError_t launch_rollout(float* d_loco, const float* d_recs, const float* d_for
                           const KModel& mdl, int batch, hipStream_t stream);
 // parity hook and JCQP condensation: full (nothing eliminated) qH [12N x 12N] / qg [12N] per
 // instance (cmpc_condense.hip)
-hipError_t launch_condense(const float* d_recs, int batch, const KParams& P, float* d_H, float* d_g,
+hipError_t launch_condense(const float* d_recs, int batch, const KParams& P, float* d_H, float* d_g, bool rows,
                            hipStream_t stream);
 // fp64 prediction, cost and optimality gap of given forces [batch x 12N] (cmpc_evaluate.hip), one
 // wavefront per instance; alpha = the force regularisation (KParams holds 2 alpha in fp32 only).

@@ -33,7 +33,7 @@ EXPORTED_SYMBOLS = (
     "f_est", "f_est_smoothed", "f_est_static",
     "cmpc_record_words", "cmpc_batch_create", "cmpc_batch_set_params", "cmpc_batch_destroy",
     "cmpc_batch_solve", "cmpc_batch_solve_host", "cmpc_batch_set_output_steps", "cmpc_batch_set_refine",
-    "cmpc_batch_condense",
+    "cmpc_batch_condense", "cmpc_batch_condense_rows",
     "cmpc_batch_stream",
     "cmpc_last_error", "cmpc_batch_enable_timing", "cmpc_batch_enable_timing_every", "cmpc_batch_read_timing", "cmpc_batch_estimate",
     "cmpc_batch_assemble", "cmpc_batch_rollout", "cmpc_batch_admm", "cmpc_batch_expand",
@@ -101,6 +101,8 @@ def load_library(path: str = LIB_PATH):
         lib.cmpc_batch_set_refine.argtypes = [ctypes.c_void_p, ctypes.c_int]
     lib.cmpc_batch_condense.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                         ctypes.c_void_p, ctypes.c_void_p]
+    if hasattr(lib, "cmpc_batch_condense_rows"):  # (older A/B variant libraries lack it)
+        lib.cmpc_batch_condense_rows.argtypes = lib.cmpc_batch_condense.argtypes
     lib.cmpc_batch_admm.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                     ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(AdmmSettings),
                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
@@ -420,12 +422,14 @@ class BatchSolver:
                "cmpc_batch_evaluate_host")
         return x_pred, cert
 
-    def condense(self, records, H, g, batch: int | None = None) -> None:
-        """Full (no elimination) qH [B,12N,12N] / qg [B,12N] on device — parity hook."""
+    def condense(self, records, H, g, batch: int | None = None, rows: bool = False) -> None:
+        """Full (no elimination) qH [B,12N,12N] / qg [B,12N] on device — parity hook.
+        ``rows``: row-owner mode (``cmpc_batch_condense_rows``): every row computes its own
+        entries on both sides of the diagonal, as class 1's two-stance rows do."""
         if batch is None:
             batch = records.shape[0]
-        _check(self.lib.cmpc_batch_condense(self._h, _ptr(records), int(batch), _ptr(H), _ptr(g)),
-               "cmpc_batch_condense")
+        fn = "cmpc_batch_condense_rows" if rows else "cmpc_batch_condense"
+        _check(getattr(self.lib, fn)(self._h, _ptr(records), int(batch), _ptr(H), _ptr(g)), fn)
 
     def admm(self, records, H, g, forces, status, iters=None, settings: AdmmSettings | None = None,
              batch: int | None = None) -> None:
