@@ -175,8 +175,9 @@ typedef struct cmpc_params {
  * of each field, the fp64 paths (the refinement of the wide classes, cmpc_batch_evaluate) the
  * doubles themselves, so the default model gives bit for bit what the literals gave.
  * Not part of the model: gravity (the reference's -9.8 in x0[12] and -9.81 in the config-5
- * residual both stay), off-diagonal body inertia (principal moments only), and a per-instance
- * model array (the handle's model is batch-shared, as cmpc_params is). */
+ * residual both stay) and off-diagonal body inertia (principal moments only). The handle's model
+ * is batch-shared, as cmpc_params is; a batch whose robots differ sets a per-instance table
+ * (cmpc_batch_set_instance_params below). */
 typedef struct cmpc_model {
   double mass;        /* kg, > 0 */
   double inertia[3];  /* principal body-frame moments Ixx, Iyy, Izz (kg m^2), each > 0;
@@ -240,6 +241,41 @@ CMPC_EXTERNC void cmpc_batch_destroy(cmpc_batch* h);
  * (the bad-value error of cmpc_batch_set_params) and leaves the handle unchanged. New API. */
 CMPC_EXTERNC int cmpc_batch_set_model(cmpc_batch* h, const cmpc_model* m);
 CMPC_EXTERNC int cmpc_batch_get_model(const cmpc_batch* h, cmpc_model* out);
+/* Per-instance robot mass, inertia, friction coefficient and force limit: one row of
+ * CMPC_INST_WORDS doubles per instance (payload and inertia randomisation per environment, a
+ * friction coefficient per terrain patch, a weakened actuator on some robots). New API. */
+#define CMPC_INST_MASS     0   /* kg, > 0                                    */
+#define CMPC_INST_INERTIA  1   /* Ixx, Iyy, Izz (kg m^2), each > 0           */
+#define CMPC_INST_MU       4   /* friction coefficient, > 0                  */
+#define CMPC_INST_FMAX     5   /* force limit (N)                            */
+#define CMPC_INST_WORDS    6
+/* d_inst: device pointer to count * CMPC_INST_WORDS doubles, 1 <= count <= max_batch. Row i belongs
+ * to instance i of every later call: the index of its record, with or without a due mask. The call
+ * snapshots the rows (later writes to d_inst have no effect until the next call) into a
+ * handle-owned table of kernel-side values, one 64-byte entry per instance, derived by the
+ * expressions the handle's own model and parameters go through ((float) inertia, 1.f / (float)
+ * mass, 1.0 / inertia, 1.0 / mass, 1.f / (float) mu, (float) f_max), so a row equal to a handle's
+ * model, mu and f_max gives that handle's bits; beside it the rows themselves (48 bytes per
+ * instance: cmpc_batch_evaluate uses the inertia doubles). Both are allocated for max_batch
+ * instances by the first call (make it outside stream capture) and freed by cmpc_batch_destroy; no
+ * solve allocates. A set-up call: it synchronises the handle's stream (a validation kernel counts
+ * the bad rows, the host reads the count, a conversion kernel fills the table).
+ * A row is bad when its mass or inertia breaks the rules of cmpc_batch_set_model (overflowing
+ * reciprocals included), when mu is not positive or 1.f / (float) mu is not finite, when (float)
+ * f_max is not finite, or when any word is non-finite. With any bad row the call returns -2 and the
+ * handle keeps its previous table, or none. d_inst == NULL clears the table: the handle is then bit
+ * for bit the handle it was before (shared model, mu and f_max).
+ * While a table is set, instance i uses row i in place of the handle's model, mu and f_max in
+ * cmpc_batch_solve, _solve_due, _solve_host, _condense, _condense_rows, _evaluate(_host), _rollout,
+ * _estimate(_due) (the residual, when d_logs is given) and _admm (fmat and U_b); a row whose
+ * |gait x f_max| < 0.01 eliminates every foot-step of that instance alone. Each of these calls with
+ * batch > count returns its bad-arguments error and writes nothing. cmpc_batch_get_model still
+ * returns the handle's shared model; cmpc_batch_set_model and _set_params still work and the table
+ * survives both: their model, mu and f_max become visible again when the table is cleared. dt,
+ * weights, alpha, horizon, max_iter, refine and output steps stay batch-shared. The single-instance
+ * surface and libcmpc_multi.so take no table. */
+CMPC_EXTERNC int cmpc_batch_set_instance_params(cmpc_batch* h, const double* d_inst, int count);
+CMPC_EXTERNC int cmpc_batch_instance_count(const cmpc_batch* h);   /* 0: none set */
 /* Device-resident solve: d_records [batch * cmpc_record_words(N)] fp32, d_forces
  * [batch * 12N] fp32 (step-major, leg*3+axis), d_status [batch] uint8, d_iters [batch] int32
  * (may be NULL). Asynchronous on the handle's stream. Returns 0 or a negative error. */

@@ -23,7 +23,8 @@ SOURCES = ["cmpc_tail.hip", "cmpc_wide_w256.hip", "cmpc_wide_w192.hip", "cmpc_cl
            "cmpc_wide_w96p.hip", "cmpc_wide_w120p.hip", "cmpc_wide_w128p.hip", "cmpc_wide_w80r.hip",
            "cmpc_wide_w96r.hip", "cmpc_wide_w120r.hip", "cmpc_wide_w80pr.hip", "cmpc_wide_w96pr.hip",
            "cmpc_wide_w120pr.hip", "cmpc_wide_w96prd.hip", "cmpc_wide_w120prd.hip", "cmpc_wide_w96rd.hip", "cmpc_wide_w120rd.hip", "cmpc_condense.hip", "cmpc_launch.hip", "cmpc_estimator.hip", "cmpc_assemble.hip",
-           "cmpc_admm.hip", "cmpc_quadprog.hip", "cmpc_evaluate.hip", "cmpc_abi.cpp"]
+           "cmpc_admm.hip", "cmpc_quadprog.hip", "cmpc_evaluate.hip", "cmpc_condense_inst.hip",
+           "cmpc_evaluate_inst.hip", "cmpc_abi.cpp"]
 ARCH = os.environ.get("CMPC_OFFLOAD_ARCH", "gfx950")
 # -fno-slp-vectorize: the SLP pass packs adjacent row updates into v_pk_fma_f32, which ties
 # slot registers into 64-bit pairs and made the register-resident rows spill

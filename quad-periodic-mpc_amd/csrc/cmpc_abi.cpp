@@ -41,6 +41,12 @@ struct cmpc_batch {
   bool own_stream = false;
   int* d_work = nullptr;
   float* d_gauss = nullptr;      // gaussian_filter kernels of the config-5 estimator
+  // per-instance table (cmpc_batch_set_instance_params): kernel-side entries, the snapshot of the
+  // caller's rows and the validation kernel's counter, allocated for max_batch by the first call
+  cmpc::KInst* d_inst = nullptr;
+  double* d_inst_rows = nullptr;
+  int* d_inst_bad = nullptr;
+  int inst_count = 0;            // rows of the table in force (0: none, kp.inst is null)
   double* d_admm_slabs = nullptr;  // ADMM inverses of QPs with n > 120 (cmpc_admm.hip)
   size_t admm_slab_doubles = 0;
   int admm_nslabs = 0;
@@ -216,6 +222,18 @@ static int ensure_admm_slabs(cmpc_batch* h) {
   return 0;
 }
 
+// kp's view of the per-instance table, after anything that rebuilt kp or changed the table. While a
+// table is set no launcher takes a literal-model build (they hold the default robot's values).
+static void apply_inst(cmpc_batch* h) {
+  h->kp.inst = h->inst_count > 0 ? h->d_inst : nullptr;
+  h->kp.mdl_default = !h->kp.inst && std::memcmp(&h->model, &kDefaultModel, sizeof h->model) == 0;
+}
+
+// a batch the handle can take: within max_batch and, with a per-instance table, within its rows
+static bool batch_ok(const cmpc_batch* h, int batch) {
+  return batch >= 0 && batch <= h->max_batch && (h->inst_count == 0 || batch <= h->inst_count);
+}
+
 extern "C" int cmpc_batch_set_params(cmpc_batch* h, const cmpc_params* prm) {
   if (!h || !prm) return -1;
   if (prm->horizon < 1 || prm->horizon > CMPC_MAX_HORIZON) {
@@ -226,6 +244,7 @@ extern "C" int cmpc_batch_set_params(cmpc_batch* h, const cmpc_params* prm) {
   h->kp = make_kparams(*prm, h->model);
   if (h->out_steps > 0 && h->out_steps < prm->horizon) h->kp.out_cols = 12 * h->out_steps;
   if (!h->refine) h->kp.refine = 0;
+  apply_inst(h);
   return ensure_admm_slabs(h);
 }
 
@@ -238,9 +257,60 @@ extern "C" int cmpc_batch_set_model(cmpc_batch* h, const cmpc_model* m) {
   }
   h->model = nm;
   h->kp.mdl = make_kmodel(nm);
-  h->kp.mdl_default = std::memcmp(&nm, &kDefaultModel, sizeof nm) == 0;
+  apply_inst(h);
   return 0;
 }
+
+extern "C" int cmpc_batch_set_instance_params(cmpc_batch* h, const double* d_inst, int count) {
+  if (!h) return -1;
+  hipError_t e;
+  if (!d_inst) {  // clear: the shared model, mu and f_max again (the buffers stay for the next table)
+    if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
+    h->inst_count = 0;
+    apply_inst(h);
+    return 0;
+  }
+  if (count < 1 || count > h->max_batch) {
+    g_last_error = "cmpc_batch_set_instance_params: count must be in 1..max_batch";
+    return -1;
+  }
+  if (!h->d_inst) {  // first call: 64 B + 48 B per instance of max_batch
+    cmpc::KInst* ent = nullptr;
+    double* rows = nullptr;
+    int* bad = nullptr;
+    if ((e = hipMalloc(&ent, sizeof(cmpc::KInst) * (size_t)h->max_batch)) != hipSuccess ||
+        (e = hipMalloc(&rows, sizeof(double) * CMPC_INST_WORDS * (size_t)h->max_batch)) != hipSuccess ||
+        (e = hipMalloc(&bad, sizeof(int))) != hipSuccess) {
+      if (ent) (void)hipFree(ent);
+      if (rows) (void)hipFree(rows);
+      return fail("hipMalloc(instance table)", e);
+    }
+    h->d_inst = ent;
+    h->d_inst_rows = rows;
+    h->d_inst_bad = bad;
+  }
+  int bad = 0;
+  if ((e = hipMemsetAsync(h->d_inst_bad, 0, sizeof(int), h->stream)) != hipSuccess) return fail("memset", e);
+  if ((e = cmpc::launch_inst_check(d_inst, count, h->d_inst_bad, h->stream)) != hipSuccess)
+    return fail("launch_inst_check", e);
+  if ((e = hipMemcpyAsync(&bad, h->d_inst_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
+    return fail("D2H", e);
+  // (also: every earlier call on the handle's stream that reads the table in force is done)
+  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
+  if (bad != 0) {
+    g_last_error = "cmpc_batch_set_instance_params: " + std::to_string(bad) +
+                   " bad row(s): mass, inertia and mu must be finite and positive, f_max finite";
+    return -2;
+  }
+  if ((e = cmpc::launch_inst_convert(d_inst, count, h->d_inst, h->d_inst_rows, h->stream)) != hipSuccess)
+    return fail("launch_inst_convert", e);
+  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
+  h->inst_count = count;
+  apply_inst(h);
+  return 0;
+}
+
+extern "C" int cmpc_batch_instance_count(const cmpc_batch* h) { return h ? h->inst_count : 0; }
 
 extern "C" int cmpc_batch_get_model(const cmpc_batch* h, cmpc_model* out) {
   if (!h || !out) return -1;
@@ -345,6 +415,9 @@ extern "C" void cmpc_batch_destroy(cmpc_batch* h) {
   if (h->d_work) (void)hipFree(h->d_work);
   if (h->d_gauss) (void)hipFree(h->d_gauss);
   if (h->d_admm_slabs) (void)hipFree(h->d_admm_slabs);
+  if (h->d_inst) (void)hipFree(h->d_inst);
+  if (h->d_inst_rows) (void)hipFree(h->d_inst_rows);
+  if (h->d_inst_bad) (void)hipFree(h->d_inst_bad);
   free_staging(h);
   for (auto e : h->ev) (void)hipEventDestroy(e);
   if (h->pooled_sides) {
@@ -370,7 +443,7 @@ extern "C" void* cmpc_batch_stream(cmpc_batch* h) { return h ? (void*)h->stream 
 
 extern "C" int cmpc_batch_solve(cmpc_batch* h, const float* d_records, int batch, float* d_forces,
                                 uint8_t* d_status, int32_t* d_iters) {
-  if (!h || batch < 0 || batch > h->max_batch || (!d_records && batch) || (!d_forces && batch) ||
+  if (!h || !batch_ok(h, batch) || (!d_records && batch) || (!d_forces && batch) ||
       (!d_status && batch)) {
     g_last_error = "cmpc_batch_solve: bad arguments";
     return -1;
@@ -390,7 +463,7 @@ extern "C" int cmpc_batch_solve(cmpc_batch* h, const float* d_records, int batch
 extern "C" int cmpc_batch_solve_due(cmpc_batch* h, const float* d_records, const uint8_t* d_due, int batch,
                                     float* d_forces, uint8_t* d_status, int32_t* d_iters) {
   if (!d_due) return cmpc_batch_solve(h, d_records, batch, d_forces, d_status, d_iters);
-  if (!h || batch < 0 || batch > h->max_batch || (!d_records && batch) || (!d_forces && batch) ||
+  if (!h || !batch_ok(h, batch) || (!d_records && batch) || (!d_forces && batch) ||
       (!d_status && batch)) {
     g_last_error = "cmpc_batch_solve_due: bad arguments";
     return -1;
@@ -408,13 +481,14 @@ extern "C" int cmpc_batch_estimate_due(cmpc_batch* h, float* d_est, const float*
                                        const float* d_fext3, const float* d_time, float sim_time,
                                        float* d_records, float* d_fext6, const uint8_t* d_due, int batch) {
   if (!d_due) return cmpc_batch_estimate(h, d_est, d_logs, d_fext3, d_time, sim_time, d_records, d_fext6, batch);
-  if (!h || batch < 0 || batch > h->max_batch || (batch && (!d_est || !d_records)) ||
+  if (!h || !batch_ok(h, batch) || (batch && (!d_est || !d_records)) ||
       (batch && !d_logs && !d_fext3)) {
     g_last_error = "cmpc_batch_estimate_due: bad arguments";
     return -1;
   }
   hipError_t e = cmpc::launch_estimate(d_est, d_logs, d_fext3, d_time, sim_time, d_records, h->kp.rec_words,
-                                       d_fext6, h->d_gauss, batch, h->stream, h->kp.mdl, nullptr, d_due);
+                                       d_fext6, h->d_gauss, batch, h->stream, h->kp.mdl, nullptr, d_due,
+                                       h->kp.inst);
   if (e != hipSuccess) return fail("launch_estimate", e);
   return 0;
 }
@@ -422,13 +496,14 @@ extern "C" int cmpc_batch_estimate_due(cmpc_batch* h, float* d_est, const float*
 extern "C" int cmpc_batch_estimate(cmpc_batch* h, float* d_est, const float* d_logs,
                                    const float* d_fext3, const float* d_time, float sim_time,
                                    float* d_records, float* d_fext6, int batch) {
-  if (!h || batch < 0 || batch > h->max_batch || (batch && (!d_est || !d_records)) ||
+  if (!h || !batch_ok(h, batch) || (batch && (!d_est || !d_records)) ||
       (batch && !d_logs && !d_fext3)) {
     g_last_error = "cmpc_batch_estimate: bad arguments";
     return -1;
   }
   hipError_t e = cmpc::launch_estimate(d_est, d_logs, d_fext3, d_time, sim_time, d_records,
-                                       h->kp.rec_words, d_fext6, h->d_gauss, batch, h->stream, h->kp.mdl);
+                                       h->kp.rec_words, d_fext6, h->d_gauss, batch, h->stream, h->kp.mdl,
+                                       nullptr, nullptr, h->kp.inst);
   if (e != hipSuccess) return fail("launch_estimate", e);
   return 0;
 }
@@ -462,13 +537,13 @@ extern "C" int cmpc_batch_expand(cmpc_batch* h, const float* d_compact, float* d
 extern "C" int cmpc_batch_rollout(cmpc_batch* h, float* d_loco, const float* d_records,
                                   const float* d_forces, const float* d_xi6, const uint8_t* d_due,
                                   int batch) {
-  if (!h || batch < 0 || batch > h->max_batch || (batch && (!d_loco || !d_records || !d_forces))) {
+  if (!h || !batch_ok(h, batch) || (batch && (!d_loco || !d_records || !d_forces))) {
     g_last_error = "cmpc_batch_rollout: bad arguments";
     return -1;
   }
   cmpc::LocoParams kp{h->kp.dt, 1, 0.f, h->kp.N, h->kp.rec_words, 0.f, 0.f, 0.f, 0.f, 0.f, h->kp.out_cols};
   hipError_t e = cmpc::launch_rollout(d_loco, d_records, d_forces, d_xi6, d_due, kp, h->kp.dt,
-                                      h->kp.mdl, batch, h->stream);
+                                      h->kp.mdl, batch, h->stream, h->kp.inst);
   if (e != hipSuccess) return fail("launch_rollout", e);
   return 0;
 }
@@ -518,7 +593,7 @@ extern "C" int cmpc_batch_read_timing(cmpc_batch* h, float* ms, int* steps_recor
 
 extern "C" int cmpc_batch_condense(cmpc_batch* h, const float* d_records, int batch, float* d_H,
                                    float* d_g) {
-  if (!h || batch < 0 || batch > h->max_batch) return -1;
+  if (!h || !batch_ok(h, batch)) return -1;
   hipError_t e = cmpc::launch_condense(d_records, batch, h->kp, d_H, d_g, false, h->stream);
   if (e != hipSuccess) return fail("launch_condense", e);
   return 0;
@@ -526,7 +601,7 @@ extern "C" int cmpc_batch_condense(cmpc_batch* h, const float* d_records, int ba
 
 extern "C" int cmpc_batch_condense_rows(cmpc_batch* h, const float* d_records, int batch, float* d_H,
                                         float* d_g) {
-  if (!h || batch < 0 || batch > h->max_batch) return -1;
+  if (!h || !batch_ok(h, batch)) return -1;
   hipError_t e = cmpc::launch_condense(d_records, batch, h->kp, d_H, d_g, true, h->stream);
   if (e != hipSuccess) return fail("launch_condense", e);
   return 0;
@@ -535,7 +610,7 @@ extern "C" int cmpc_batch_condense_rows(cmpc_batch* h, const float* d_records, i
 extern "C" int cmpc_batch_admm(cmpc_batch* h, const float* d_records, const float* d_H,
                                const float* d_g, int batch, const cmpc_admm_settings* s,
                                float* d_forces, uint8_t* d_status, int32_t* d_iters) {
-  if (!h || !s || batch < 0 || batch > h->max_batch ||
+  if (!h || !s || !batch_ok(h, batch) ||
       (batch && (!d_records || !d_H || !d_g || !d_forces || !d_status))) {
     g_last_error = "cmpc_batch_admm: bad arguments";
     return -1;
@@ -662,14 +737,15 @@ static int solve_single_host(cmpc_batch* h, const float* record, float* forces, 
 
 extern "C" int cmpc_batch_solve_host(cmpc_batch* h, const float* records, int batch, float* forces,
                                      uint8_t* status, int32_t* iters) {
-  if (!h || batch < 0 || batch > h->max_batch) return -1;
+  if (!h || !batch_ok(h, batch)) return -1;
   if (batch == 0) return 0;
   if (int r = ensure_staging(h)) return r;
   const int N = h->prm.horizon;
   const size_t rw = (size_t)CMPC_REC_WORDS(N);
   // one instance (the reference ABI's operating mode): the fast path, unless per-launch timing
   // is on (it brackets the batched launch sequence)
-  if (batch == 1 && h->ev_steps == 0) return solve_single_host(h, records, forces, status, iters);
+  // (with a per-instance table the batched sequence: its classify pass reads the row's f_max)
+  if (batch == 1 && h->ev_steps == 0 && h->inst_count == 0) return solve_single_host(h, records, forces, status, iters);
   hipError_t e;
   if ((e = hipMemcpyAsync(h->d_rec, records, rw * batch * sizeof(float), hipMemcpyHostToDevice, h->stream)) != hipSuccess)
     return fail("H2D", e);
@@ -687,7 +763,7 @@ extern "C" int cmpc_batch_solve_host(cmpc_batch* h, const float* records, int ba
 
 extern "C" int cmpc_batch_evaluate(cmpc_batch* h, const float* d_records, const float* d_forces, int batch,
                                    float* d_xpred, double* d_cert) {
-  if (!h || batch < 0 || batch > h->max_batch || (batch && (!d_records || !d_forces))) {
+  if (!h || !batch_ok(h, batch) || (batch && (!d_records || !d_forces))) {
     g_last_error = "cmpc_batch_evaluate: bad arguments";
     return -1;
   }
@@ -700,14 +776,14 @@ extern "C" int cmpc_batch_evaluate(cmpc_batch* h, const float* d_records, const 
     return -3;
   }
   const hipError_t e = cmpc::launch_evaluate(d_records, d_forces, batch, h->kp, (double)h->prm.alpha,
-                                             h->model.inertia, d_xpred, d_cert, h->stream);
+                                             h->model.inertia, d_xpred, d_cert, h->stream, h->d_inst_rows);
   if (e != hipSuccess) return fail("launch_evaluate", e);
   return 0;
 }
 
 extern "C" int cmpc_batch_evaluate_host(cmpc_batch* h, const float* records, const float* forces, int batch,
                                         float* xpred, double* cert) {
-  if (!h || batch < 0 || batch > h->max_batch || (batch && (!records || !forces))) {
+  if (!h || !batch_ok(h, batch) || (batch && (!records || !forces))) {
     g_last_error = "cmpc_batch_evaluate_host: bad arguments";
     return -1;
   }

@@ -88,12 +88,14 @@ struct AdmmShared {
 // One instance by one workgroup. M: the n x n Schur complement / its inverse, in LDS (n <= 120)
 // or in this workgroup's global slab. Returns false (nothing written) when the instance's n is
 // outside [n_lo, NV] — another launch owns it.
-template <int NV, int NC, bool GM>
+// INST (a handle with a per-instance table): fmat's 1 / mu and U_b's f_max of instance i from
+// entry i of tab (uniform over the workgroup).
+template <int NV, int NC, bool GM, bool INST = false>
 __device__ bool admm_solve(const float* __restrict__ recs, const float* __restrict__ gH,
                            const float* __restrict__ gg, const AdmmParams& ap,
                            float* __restrict__ forces, uint8_t* __restrict__ status,
                            int32_t* __restrict__ iters, int inst, double* __restrict__ M,
-                           AdmmShared<NV, NC>& sh, int n_lo) {
+                           AdmmShared<NV, NC>& sh, int n_lo, const KInst* __restrict__ tab = nullptr) {
   double(&sx)[2][NV] = sh.sx;
   auto& sz = sh.sz;
   double* sy = sh.sy;
@@ -110,7 +112,12 @@ __device__ bool admm_solve(const float* __restrict__ recs, const float* __restri
   const float* H = gH + (size_t)inst * nf * nf;
   const float* rec = recs + (size_t)inst * ap.rec_words;
   const uint8_t* gait = reinterpret_cast<const uint8_t*>(rec + CMPC_REC_HDR + 12 * ap.N);
-  const double mi = (double)ap.mu_inv;
+  float mu_inv = ap.mu_inv, f_max = ap.f_max;
+  if constexpr (INST) {
+    mu_inv = tab[inst].mu_inv;
+    f_max = tab[inst].f_max;
+  }
+  const double mi = (double)mu_inv;
   // Elimination (reduced mode): a foot-step whose fz row has lb = ub = 0 (gait 0) loses its three
   // variables and five rows; the kept ones stay in order (SolverMPC.cpp:859-950)
   __syncthreads();   // the previous instance of a persistent workgroup is done with sh
@@ -141,7 +148,7 @@ __device__ bool admm_solve(const float* __restrict__ recs, const float* __restri
   for (int r = t; r < m; r += kAdmmThreads) {
     const int b = r / 5, k = r - 5 * b;
     // U_b (SolverMPC.cpp:646-652): 5e10 for the four pyramid rows, gait * f_max for fz
-    const double u = k < 4 ? (double)5e10f : (double)((float)gait[smap[b]] * ap.f_max);
+    const double u = k < 4 ? (double)5e10f : (double)((float)gait[smap[b]] * f_max);
     double rho;
     if (u > 1e10) rho = 1e-6;                        // INFINITE: rhoInfty
     else if (fabs(u) < 1e-10) rho = ap.rho * 1e3;   // EQUALITY: rho * rhoEqualityScale
@@ -310,6 +317,29 @@ cmpc_admm_gm_kernel(const float* __restrict__ recs, const float* __restrict__ gH
     admm_solve<kGNV, kGNC, true>(recs, gH, gg, ap, forces, status, iters, inst, M, sh, kNV + 1);
 }
 
+// the two kernels above for a handle with a per-instance table (kernels of their own names)
+__global__ void __launch_bounds__(kAdmmThreads)
+cmpc_admm_inst_kernel(const float* __restrict__ recs, const float* __restrict__ gH,
+                      const float* __restrict__ gg, AdmmParams ap, float* __restrict__ forces,
+                      uint8_t* __restrict__ status, int32_t* __restrict__ iters,
+                      const KInst* __restrict__ tab) {
+  __shared__ double M[kNV * kNV];
+  __shared__ AdmmShared<kNV, kNC> sh;
+  admm_solve<kNV, kNC, false, true>(recs, gH, gg, ap, forces, status, iters, blockIdx.x, M, sh, 0, tab);
+}
+
+__global__ void __launch_bounds__(kAdmmThreads)
+cmpc_admm_gm_inst_kernel(const float* __restrict__ recs, const float* __restrict__ gH,
+                         const float* __restrict__ gg, AdmmParams ap, float* __restrict__ forces,
+                         uint8_t* __restrict__ status, int32_t* __restrict__ iters, int batch,
+                         double* __restrict__ slabs, const KInst* __restrict__ tab) {
+  __shared__ AdmmShared<kGNV, kGNC> sh;
+  const int nf = 12 * ap.N;
+  double* M = slabs + (size_t)blockIdx.x * nf * nf;
+  for (int inst = blockIdx.x; inst < batch; inst += gridDim.x)
+    admm_solve<kGNV, kGNC, true, true>(recs, gH, gg, ap, forces, status, iters, inst, M, sh, kNV + 1, tab);
+}
+
 }  // namespace
 
 size_t admm_slab_doubles(int horizon) { return (size_t)144 * horizon * horizon; }
@@ -327,6 +357,16 @@ hipError_t launch_admm(const float* d_recs, const float* d_H, const float* d_g, 
   const bool small_possible = s.reduced || P.N <= kAdmmMaxN;
   const bool large_possible = 12 * P.N > kNV;
   if (large_possible && (!d_slabs || nslabs < 1)) return hipErrorInvalidValue;
+  if (P.inst) {
+    if (small_possible)
+      hipLaunchKernelGGL(cmpc_admm_inst_kernel, dim3(batch), dim3(kAdmmThreads), 0, stream, d_recs, d_H,
+                         d_g, ap, d_forces, d_status, d_iters, P.inst);
+    if (large_possible)
+      hipLaunchKernelGGL(cmpc_admm_gm_inst_kernel, dim3(batch < nslabs ? batch : nslabs),
+                         dim3(kAdmmThreads), 0, stream, d_recs, d_H, d_g, ap, d_forces, d_status,
+                         d_iters, batch, d_slabs, P.inst);
+    return hipGetLastError();
+  }
   if (small_possible)
     hipLaunchKernelGGL(cmpc_admm_kernel, dim3(batch), dim3(kAdmmThreads), 0, stream, d_recs, d_H,
                        d_g, ap, d_forces, d_status, d_iters);

@@ -316,15 +316,17 @@ __global__ __launch_bounds__(256) void cmpc_assemble_kernel(float* __restrict__ 
 // CMPC_LOCO_SIMFEET the assemble kernel moves them (swing feet on their Bezier trajectory, touch
 // down at the foothold Pf, stance feet fixed in the world) and the rollout leaves them alone;
 // without it they keep their offset from the body in x and y. One thread per instance.
-__global__ __launch_bounds__(256) void cmpc_rollout_kernel(float* __restrict__ loco,
-                                                           const float* __restrict__ recs,
-                                                           const float* __restrict__ forces,
-                                                           const float* __restrict__ xi6,
-                                                           const uint8_t* __restrict__ due,
-                                                           LocoParams lp, float dt, KModel mdl,
-                                                           int batch) {
+// inst (a handle with a per-instance table, else null): instance i steps with the model of entry i.
+__device__ __forceinline__ void rollout_one(float* __restrict__ loco, const float* __restrict__ recs,
+                                            const float* __restrict__ forces, const float* __restrict__ xi6,
+                                            const uint8_t* __restrict__ due, const LocoParams& lp, float dt,
+                                            KModel mdl, int batch, const KInst* __restrict__ inst) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= batch || (due && !due[i])) return;
+  if (inst) {  // the entry's fp32 block {ib, im}: all the step uses of the model
+    const float4 m4 = *reinterpret_cast<const float4*>(&inst[i]);
+    mdl.ib[0] = m4.x; mdl.ib[1] = m4.y; mdl.ib[2] = m4.z; mdl.im = m4.w;
+  }
   const float* rec = recs + (size_t)i * lp.rec_words;
   const float* u = forces + (size_t)i * lp.out_cols;  // step 0: 12 forces, leg * 3 + axis
   Model md;
@@ -407,6 +409,26 @@ __global__ __launch_bounds__(256) void cmpc_rollout_kernel(float* __restrict__ l
   s[CMPC_LOCO_Q + 3] = cr * cp * sy - sr * sp * cy;
 }
 
+__global__ __launch_bounds__(256) void cmpc_rollout_kernel(float* __restrict__ loco,
+                                                           const float* __restrict__ recs,
+                                                           const float* __restrict__ forces,
+                                                           const float* __restrict__ xi6,
+                                                           const uint8_t* __restrict__ due,
+                                                           LocoParams lp, float dt, KModel mdl,
+                                                           int batch) {
+  rollout_one(loco, recs, forces, xi6, due, lp, dt, mdl, batch, nullptr);
+}
+
+__global__ __launch_bounds__(256) void cmpc_rollout_inst_kernel(float* __restrict__ loco,
+                                                                const float* __restrict__ recs,
+                                                                const float* __restrict__ forces,
+                                                                const float* __restrict__ xi6,
+                                                                const uint8_t* __restrict__ due,
+                                                                LocoParams lp, float dt, KModel mdl,
+                                                                int batch, const KInst* __restrict__ inst) {
+  rollout_one(loco, recs, forces, xi6, due, lp, dt, mdl, batch, inst);
+}
+
 // Compact records -> solve records (include/cmpc_solver.h CMPC_CREC_*): the header as is, trajAll
 // per updateMPCIfNeeded (ConvexMPCLocomotion.cpp:554-585) from its step-0 row — every step the
 // step-0 row, except trajAll[12 k + 2/3/4] = trajAll[12 (k-1) + 2/3/4] + dtMPC x (yaw rate, v_x,
@@ -452,8 +474,13 @@ hipError_t launch_assemble(float* d_loco, const LocoParams& lp, float* d_recs, u
 
 hipError_t launch_rollout(float* d_loco, const float* d_recs, const float* d_forces,
                           const float* d_xi6, const uint8_t* d_due, const LocoParams& lp, float dt,
-                          const KModel& mdl, int batch, hipStream_t stream) {
+                          const KModel& mdl, int batch, hipStream_t stream, const KInst* inst) {
   if (batch <= 0) return hipSuccess;
+  if (inst) {
+    hipLaunchKernelGGL(cmpc_rollout_inst_kernel, dim3((batch + 255) / 256), dim3(256), 0, stream, d_loco,
+                       d_recs, d_forces, d_xi6, d_due, lp, dt, mdl, batch, inst);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(cmpc_rollout_kernel, dim3((batch + 255) / 256), dim3(256), 0, stream, d_loco,
                      d_recs, d_forces, d_xi6, d_due, lp, dt, mdl, batch);
   return hipGetLastError();

@@ -310,7 +310,10 @@ __device__ __forceinline__ float pick_col(const float (&x)[MA], int q) {
 // pointers (forces, status, iters, one after the other) in its argument segment. The outputs are
 // then read where the instance is written out (karg_late), not held in six SGPRs from kernel
 // entry, and fout / st_out / it_out are not used.
-template <int NV, int POFF = -1, int OOFF = -1>
+// INST: the per-instance build (cmpc_batch_set_instance_params). The instance's table entry
+// P.inst[inst] gives the model, f_max and 1 / mu in place of P.mdl, P.f_max and P.mu_inv: scalar
+// loads at a wave-uniform address (inst_late), each where the shared build first reads its value.
+template <int NV, int POFF = -1, int OOFF = -1, bool INST = false>
 __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KParams& P,
                                          SharedC1<NV>& sh, float* __restrict__ fout,
                                          uint8_t* __restrict__ st_out, int32_t* __restrict__ it_out,
@@ -333,6 +336,12 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
   }
   lsync();
   const float* srec = &sh.P[OFF_REC];
+  const KInst* ie = nullptr;  // this instance's table entry (uniform)
+  float f_max = P.f_max;
+  if constexpr (INST) {
+    ie = inst_entry(P, inst);
+    f_max = inst_late<float>(ie, kInstFmaxOff);
+  }
   // ---- stance table + elimination: eliminated iff |gait * f_max| < 0.01 (SolverMPC.cpp:869-894)
   const unsigned char* gait = reinterpret_cast<const unsigned char*>(srec + CMPC_REC_HDR + 12 * N);
   int nfs = 0;
@@ -342,7 +351,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
     float ub = 0.f;
     bool f = false;
     if (t < 4 * N) {
-      ub = (float)gait[t] * P.f_max;
+      ub = (float)gait[t] * f_max;
       f = !(ub < 0.01f && ub > -0.01f);
     }
     const unsigned long long m = __ballot(f);
@@ -378,7 +387,8 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
     for (int t = v; t < nfs; t += 64) sh.cmask[t] = 0;
   }
   Model md;
-  make_model(srec, P.dt, P.mdl, md);
+  if constexpr (INST) make_model<kModelFromInst>(srec, P.dt, P.mdl, md, ie);
+  else make_model(srec, P.dt, P.mdl, md);
   make_bdt<64>(srec, md, v, sh.u.BdtT);
   CondGeo cg;
   make_cond_geo<true>(srec, md, cg);
@@ -956,7 +966,8 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
   // registers see the same straight-line code on every trip — a Householder reflection (the
   // add step; beta = 0 on a drop) and an ascending Givens chain (the drop step; identity
   // rotations otherwise) — so their registers carry through the loop without copies.
-  const float mui = P.mu_inv;
+  float mui = P.mu_inv;
+  if constexpr (INST) mui = inst_late<float>(ie, kInstMuInvOff);
   const float fnorm = rsqrtf(mui * mui + 1.f);
   int q = 0;
   int iters = 0;
@@ -1280,6 +1291,39 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
 
 }  // namespace
 
+// the per-instance build of the kernel below (its body with solve_c1's INST set; a kernel of its
+// own name, so the shared build keeps its name and its registers)
+template <int NV>
+__global__ __launch_bounds__(64, NV == 60 ? CMPC_W1_WAVES_60 : CMPC_W1_WAVES_PER_EU) void cmpc_solve_c1_inst_kernel(
+    const float* __restrict__ recs, int batch, KParams P, float* __restrict__ forces,
+    uint8_t* __restrict__ status, int32_t* __restrict__ iters, const int* __restrict__ in_list,
+    const int* __restrict__ in_count, int* __restrict__ ovf_list, int* __restrict__ ovf_count) {
+  __shared__ SharedC1<NV> sh;
+  int t = blockIdx.x;
+  if (in_list) {
+    if (t >= *in_count) return;
+    t = in_list[t];
+  } else if (t >= batch) {
+    return;
+  }
+#if CMPC_C1_STATIC2
+  using K = decltype(&cmpc_solve_c1_inst_kernel<NV>);
+  using KP = KArg<2, K>;
+  static_assert(std::is_same<typename KP::type, KParams>::value, "argument 2 is the KParams");
+  static_assert(std::is_same<typename KArg<3, K>::type, float*>::value &&
+                    std::is_same<typename KArg<4, K>::type, uint8_t*>::value &&
+                    std::is_same<typename KArg<5, K>::type, int32_t*>::value &&
+                    KArg<4, K>::offset() == KArg<3, K>::offset() + 8 &&
+                    KArg<5, K>::offset() == KArg<3, K>::offset() + 16,
+                "arguments 3..5 are forces, status, iters");
+  solve_c1<NV, KP::offset(), KArg<3, K>::offset(), true>(recs + (size_t)t * P.rec_words, P, sh, nullptr, nullptr,
+                                                         nullptr, ovf_list, ovf_count, t);
+#else
+  solve_c1<NV, -1, -1, true>(recs + (size_t)t * P.rec_words, P, sh, forces + (size_t)t * P.out_cols, status + t,
+                             iters ? iters + t : nullptr, ovf_list, ovf_count, t);
+#endif
+}
+
 template <int NV>
 __global__ __launch_bounds__(64, NV == 60 ? CMPC_W1_WAVES_60 : CMPC_W1_WAVES_PER_EU) void cmpc_solve_c1_kernel(
     const float* __restrict__ recs, int batch, KParams P, float* __restrict__ forces,
@@ -1334,6 +1378,15 @@ hipError_t launch_class1(int nv, const float* d_recs, int batch, const KParams& 
   // CMPC_C1_DYN_LDS=<bytes> (diagnostic build only): extra dynamic LDS per workgroup, i.e. fewer class-1
   // workgroups per CU (placement / occupancy experiments)
   static const unsigned dyn = (unsigned)diag_knob("CMPC_C1_DYN_LDS", 0);
+  if (P.inst) {  // the per-instance builds
+    if (nv == 60)
+      hipLaunchKernelGGL(cmpc_solve_c1_inst_kernel<60>, dim3(grid), dim3(64), dyn, stream, d_recs, batch, P,
+                         d_forces, d_status, d_iters, in_list, in_count, ovf_list, ovf_count);
+    else
+      hipLaunchKernelGGL(cmpc_solve_c1_inst_kernel<64>, dim3(grid), dim3(64), dyn, stream, d_recs, batch, P,
+                         d_forces, d_status, d_iters, in_list, in_count, ovf_list, ovf_count);
+    return hipGetLastError();
+  }
   if (nv == 60)
     hipLaunchKernelGGL(cmpc_solve_c1_kernel<60>, dim3(grid), dim3(64), dyn, stream, d_recs, batch, P,
                        d_forces, d_status, d_iters, in_list, in_count, ovf_list, ovf_count);

@@ -515,6 +515,28 @@ typedef double kf64x4 __attribute__((ext_vector_type(4), aligned(8)));
 static_assert(offsetof(KModel, ib) == 0 && offsetof(KModel, im) == 12 && offsetof(KModel, iinv64) == 16 &&
               offsetof(KModel, im64) == 40, "KModel = {ib[3], im} {iinv64[3], im64}");
 
+// The per-instance builds' counterpart of karg_late: a value of the instance's table entry
+// (KParams::inst + instance, a wave-uniform address of read-only global memory), re-read where it
+// is used by a scalar load behind a pointer the optimiser cannot see through. Loads only: nothing
+// is ever written through the scalar path.
+template <typename T>
+__device__ __forceinline__ T inst_late(const KInst* e, int off) {
+  typedef const __attribute__((address_space(4))) char* cptr;
+  cptr p = (cptr)(uintptr_t)e;
+  asm volatile("" : "+s"(p));
+  return *reinterpret_cast<const __attribute__((address_space(4))) T*>(p + off);
+}
+// the entry of instance `inst` (uniform over the wavefront: the index is forced into an SGPR)
+__device__ __forceinline__ const KInst* inst_entry(const KParams& P, int inst) {
+  return P.inst + __builtin_amdgcn_readfirstlane(inst);
+}
+constexpr int kInstMuInvOff = (int)offsetof(KInst, mu_inv);
+constexpr int kInstFmaxOff = (int)offsetof(KInst, f_max);
+constexpr int kInstIinv64Off = (int)(offsetof(KInst, mdl) + offsetof(KModel, iinv64));
+constexpr int kInstIm64Off = (int)(offsetof(KInst, mdl) + offsetof(KModel, im64));
+// make_model's MOFF of a per-instance build: the model's fp32 values come from the table entry
+constexpr int kModelFromInst = -2;
+
 // Byte offset and type of argument I of a kernel in its argument segment, from the kernel's own
 // signature (K = decltype(&kernel)): every argument lies at its natural alignment
 template <int I, class K>
@@ -536,9 +558,10 @@ struct KArg<I, void (*)(A...)> {
 // quaternion (w,x,y,z) -> rotation matrix, as Eigen's toRotationMatrix (RobotState.cpp:36).
 // MOFF >= 0: the byte offset of the kernel's KModel in its argument segment; the model's fp32
 // values are then read through karg_late, per instance, instead of from km.
+// MOFF == kModelFromInst: from the instance's table entry ie (one 16-byte scalar load) instead.
 template <int MOFF = -1>
 __device__ __forceinline__ void make_model(const float* __restrict__ rec, float dt, const KModel& km,
-                                           Model& md) {
+                                           Model& md, const KInst* ie = nullptr) {
   const float qw = rec[CMPC_REC_Q + 0], qx = rec[CMPC_REC_Q + 1], qy = rec[CMPC_REC_Q + 2],
               qz = rec[CMPC_REC_Q + 3];
   const float tx = 2.f * qx, ty = 2.f * qy, tz = 2.f * qz;
@@ -551,7 +574,13 @@ __device__ __forceinline__ void make_model(const float* __restrict__ rec, float 
   md.dt = dt;
   md.dth = dt * dt * 0.5f;
   md.xdrag = rec[CMPC_REC_XDRAG];
-  if constexpr (MOFF >= 0) {
+  if constexpr (MOFF == kModelFromInst) {
+    const kf32x4 m4 = inst_late<kf32x4>(ie, 0);
+    md.ib[0] = m4.x;
+    md.ib[1] = m4.y;
+    md.ib[2] = m4.z;
+    md.im = m4.w;
+  } else if constexpr (MOFF >= 0) {
     const kf32x4 m4 = karg_late<kf32x4>(MOFF);
     md.ib[0] = m4.x;
     md.ib[1] = m4.y;

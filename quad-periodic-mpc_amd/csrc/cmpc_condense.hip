@@ -8,6 +8,12 @@
 // z_i = Adt' z_{i+1}, the source term masked off) and writes its own entries on both sides of the
 // diagonal, nothing mirrored: what class 1's two-stance rows compute (cmpc_class1.hip,
 // CMPC_C1_STATIC2), here under the fp64 check of the parity hook.
+// CMPC_CONDENSE_INST = 1 (cmpc_condense_inst.hip, which includes this file): the per-instance build
+// for a handle with a table (cmpc_batch_set_instance_params), a kernel and a launcher of their own
+// names in a unit of their own, so that this unit compiles the shared kernel exactly as before.
+#ifndef CMPC_CONDENSE_INST
+#define CMPC_CONDENSE_INST 0
+#endif
 #include "cmpc_common.h"
 
 namespace cmpc {
@@ -88,6 +94,21 @@ __device__ void condense_one(const float* __restrict__ rec, const KParams& P, Sh
   }
 }
 
+#if CMPC_CONDENSE_INST
+// instance i under the model of its table entry: the shared parameters with that entry's model
+__global__ __launch_bounds__(NTG) void cmpc_condense_inst_kernel(const float* __restrict__ recs, int batch, KParams P,
+                                                                 float* __restrict__ Hout, float* __restrict__ gout,
+                                                                 int rows) {
+  __shared__ SharedC sh;
+  const size_t n = 12 * (size_t)P.N;
+  for (int inst = blockIdx.x; inst < batch; inst += gridDim.x) {
+    KParams Pi = P;
+    Pi.mdl = P.inst[inst].mdl;
+    condense_one(recs + (size_t)inst * P.rec_words, Pi, sh, Hout + inst * n * n, gout + inst * n, rows != 0);
+    __syncthreads();
+  }
+}
+#else
 __global__ __launch_bounds__(NTG) void cmpc_condense_kernel(const float* __restrict__ recs, int batch, KParams P,
                                                             float* __restrict__ Hout, float* __restrict__ gout,
                                                             int rows) {
@@ -99,15 +120,31 @@ __global__ __launch_bounds__(NTG) void cmpc_condense_kernel(const float* __restr
   }
 }
 
+#endif
+
 }  // namespace
+
+#if CMPC_CONDENSE_INST
+hipError_t launch_condense_inst(const float* d_recs, int batch, const KParams& P, float* d_H, float* d_g,
+                                bool rows, hipStream_t stream) {
+  const int grid = batch < 2048 ? batch : 2048;
+  hipLaunchKernelGGL(cmpc_condense_inst_kernel, dim3(grid), dim3(NTG), 0, stream, d_recs, batch, P, d_H, d_g,
+                     rows ? 1 : 0);
+  return hipGetLastError();
+}
+#else
+hipError_t launch_condense_inst(const float* d_recs, int batch, const KParams& P, float* d_H, float* d_g,
+                                bool rows, hipStream_t stream);  // cmpc_condense_inst.hip
 
 hipError_t launch_condense(const float* d_recs, int batch, const KParams& P, float* d_H, float* d_g,
                            bool rows, hipStream_t stream) {
   if (batch <= 0) return hipSuccess;
+  if (P.inst) return launch_condense_inst(d_recs, batch, P, d_H, d_g, rows, stream);
   const int grid = batch < 2048 ? batch : 2048;
   hipLaunchKernelGGL(cmpc_condense_kernel, dim3(grid), dim3(NTG), 0, stream, d_recs, batch, P, d_H, d_g,
                      rows ? 1 : 0);
   return hipGetLastError();
 }
+#endif
 
 }  // namespace cmpc

@@ -257,7 +257,9 @@ __device__ __forceinline__ void estimate_step(
     float* __restrict__ est, const float* __restrict__ logs, const float* __restrict__ fext3,
     const float* __restrict__ times, float sim_time, float* __restrict__ recs, int rec_words,
     float* __restrict__ fext6, const float* __restrict__ gauss, int batch, float* __restrict__ fest_out,
-    const uint8_t* __restrict__ due, float4 mdl) {
+    const uint8_t* __restrict__ due, float4 mdl, const KInst* __restrict__ inst_tab = nullptr) {
+  // inst_tab (a handle with a per-instance table, else null): the residual of instance i under the
+  // model of entry i (its fp32 block {ib, im})
   __shared__ SharedE sh;
   const int inst = blockIdx.x;
   if (inst >= batch) return;
@@ -270,6 +272,7 @@ __device__ __forceinline__ void estimate_step(
     float f3;
     if (logs) {
       float fe[6];
+      if (inst_tab) mdl = *reinterpret_cast<const float4*>(&inst_tab[inst]);
       residual(logs + (size_t)inst * CMPC_LOG_WORDS, rec, mdl, fe);
       f3 = fe[3];
       if (fext6) {
@@ -401,14 +404,43 @@ __global__ __launch_bounds__(NT) void cmpc_estimate_due_kernel(
                       mdl);
 }
 
+// the two kernels above for a handle with a per-instance table (kernels of their own names)
+__global__ __launch_bounds__(NT) void cmpc_estimate_inst_kernel(
+    float* __restrict__ est, const float* __restrict__ logs, const float* __restrict__ fext3,
+    const float* __restrict__ times, float sim_time, float* __restrict__ recs, int rec_words,
+    float* __restrict__ fext6, const float* __restrict__ gauss, int batch, float* __restrict__ fest_out,
+    float4 mdl, const KInst* __restrict__ inst_tab) {
+  estimate_step<false>(est, logs, fext3, times, sim_time, recs, rec_words, fext6, gauss, batch, fest_out,
+                       nullptr, mdl, inst_tab);
+}
+
+__global__ __launch_bounds__(NT) void cmpc_estimate_due_inst_kernel(
+    float* __restrict__ est, const float* __restrict__ logs, const float* __restrict__ fext3,
+    const float* __restrict__ times, float sim_time, float* __restrict__ recs, int rec_words,
+    float* __restrict__ fext6, const float* __restrict__ gauss, int batch, float* __restrict__ fest_out,
+    const uint8_t* __restrict__ due, float4 mdl, const KInst* __restrict__ inst_tab) {
+  estimate_step<true>(est, logs, fext3, times, sim_time, recs, rec_words, fext6, gauss, batch, fest_out, due,
+                      mdl, inst_tab);
+}
+
 }  // namespace
 
 hipError_t launch_estimate(float* d_est, const float* d_logs, const float* d_fext3,
                            const float* d_time, float sim_time, float* d_records, int rec_words,
                            float* d_fext6, const float* d_gauss, int batch, hipStream_t stream,
-                           const KModel& mdl, float* d_fest_out, const uint8_t* d_due) {
+                           const KModel& mdl, float* d_fest_out, const uint8_t* d_due, const KInst* inst) {
   if (batch <= 0) return hipSuccess;
   const float4 m4 = make_float4(mdl.ib[0], mdl.ib[1], mdl.ib[2], mdl.im);  // read by the residual only
+  if (inst && d_logs) {  // (without logs no residual is formed and the model is not read)
+    if (d_due)
+      hipLaunchKernelGGL(cmpc_estimate_due_inst_kernel, dim3(batch), dim3(NT), 0, stream, d_est, d_logs, d_fext3,
+                         d_time, sim_time, d_records, rec_words, d_fext6, d_gauss, batch, d_fest_out, d_due, m4,
+                         inst);
+    else
+      hipLaunchKernelGGL(cmpc_estimate_inst_kernel, dim3(batch), dim3(NT), 0, stream, d_est, d_logs, d_fext3,
+                         d_time, sim_time, d_records, rec_words, d_fext6, d_gauss, batch, d_fest_out, m4, inst);
+    return hipGetLastError();
+  }
   if (d_due)
     hipLaunchKernelGGL(cmpc_estimate_due_kernel, dim3(batch), dim3(NT), 0, stream, d_est, d_logs, d_fext3,
                        d_time, sim_time, d_records, rec_words, d_fext6, d_gauss, batch, d_fest_out, d_due, m4);

@@ -19,6 +19,9 @@
 //   E  lane (k, f): the gradient of foot-step (k, f), (y_k x r_f) + nu_k[9:12]/m + 2 alpha u, and
 //      its gap / slack / swing terms
 //   F  xor-butterfly reductions over the wave: the same order for every instance, whatever the batch
+#ifndef CMPC_EVALUATE_INST
+#define CMPC_EVALUATE_INST 0  // 1: the per-instance build (cmpc_evaluate_inst.hip; see the kernel below)
+#endif
 #include "cmpc_common.h"
 
 namespace cmpc {
@@ -66,6 +69,30 @@ __device__ __forceinline__ double bfly_max(double v) {
   return v;
 }
 
+// CMPC_EVALUATE_INST = 1 (cmpc_evaluate_inst.hip, which includes this file): the per-instance build
+// for a handle with a table (cmpc_batch_set_instance_params), a kernel and a launcher of their own
+// names in a unit of their own, so that this unit compiles the shared kernel exactly as before. The
+// kernel's body is the one below: instance i first takes its inertia doubles from row i of the
+// handle's snapshot of the caller's rows and 1 / m, 1 / mu and f_max from its table entry.
+#if CMPC_EVALUATE_INST
+__global__ __launch_bounds__(64) void cmpc_evaluate_inst_kernel(const float* __restrict__ d_recs,
+                                                                const float* __restrict__ d_forces, int batch,
+                                                                KParams P, double alpha,
+                                                                const double* __restrict__ inst_rows,
+                                                                float* __restrict__ d_xpred,
+                                                                double* __restrict__ d_cert) {
+  __shared__ EvalShared sh;
+  const int inst = blockIdx.x;
+  if (inst >= batch) return;
+  const double* row = inst_rows + (size_t)inst * CMPC_INST_WORDS;
+  const double ib0 = row[CMPC_INST_INERTIA], ib1 = row[CMPC_INST_INERTIA + 1], ib2 = row[CMPC_INST_INERTIA + 2];
+  {
+    const KInst* e = P.inst + inst;
+    P.mdl.im64 = e->mdl.im64;
+    P.mu_inv = e->mu_inv;
+    P.f_max = e->f_max;
+  }
+#else
 __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restrict__ d_recs,
                                                            const float* __restrict__ d_forces, int batch,
                                                            KParams P, double alpha, double ib0,
@@ -75,6 +102,7 @@ __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restri
   __shared__ EvalShared sh;
   const int inst = blockIdx.x;
   if (inst >= batch) return;
+#endif
   const int lane = threadIdx.x;
   const int N = P.N;
   const float* __restrict__ rec = d_recs + (size_t)inst * P.rec_words;
@@ -329,13 +357,30 @@ __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restri
 
 }  // namespace
 
+#if CMPC_EVALUATE_INST
+hipError_t launch_evaluate_inst(const float* d_recs, const float* d_forces, int batch, const KParams& P,
+                                double alpha, const double* inst_rows, float* d_xpred, double* d_cert,
+                                hipStream_t stream) {
+  hipLaunchKernelGGL(cmpc_evaluate_inst_kernel, dim3(batch), dim3(64), 0, stream, d_recs, d_forces, batch, P,
+                     alpha, inst_rows, d_xpred, d_cert);
+  return hipGetLastError();
+}
+#else
+hipError_t launch_evaluate_inst(const float* d_recs, const float* d_forces, int batch, const KParams& P,
+                                double alpha, const double* inst_rows, float* d_xpred, double* d_cert,
+                                hipStream_t stream);  // cmpc_evaluate_inst.hip
+
 hipError_t launch_evaluate(const float* d_recs, const float* d_forces, int batch, const KParams& P,
                            double alpha, const double* ib64, float* d_xpred, double* d_cert,
-                           hipStream_t stream) {
+                           hipStream_t stream, const double* inst_rows) {
   if (batch <= 0) return hipSuccess;
+  if (P.inst)
+    return inst_rows ? launch_evaluate_inst(d_recs, d_forces, batch, P, alpha, inst_rows, d_xpred, d_cert, stream)
+                     : hipErrorInvalidValue;
   hipLaunchKernelGGL(cmpc_evaluate_kernel, dim3(batch), dim3(64), 0, stream, d_recs, d_forces, batch, P,
                      alpha, ib64[0], ib64[1], ib64[2], d_xpred, d_cert);
   return hipGetLastError();
 }
+#endif
 
 }  // namespace cmpc

@@ -1,6 +1,7 @@
 // cmpc_kernels.h — internal interface between the HIP kernels and the C-ABI host layer.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -32,6 +33,20 @@ struct KModel {
   double im64;       // 1.0 / mass
 };
 
+// One row of a handle's per-instance table (cmpc_batch_set_instance_params): what instance i uses
+// in place of the handle's model, mu and f_max. KModel first, so the fp32 block {ib, im} and the
+// fp64 block {iinv64, im64} sit at the offsets they have in the argument segment's KModel and one
+// scalar load each fetches them; 64 bytes, so an entry never straddles a cache line. (The inertia
+// doubles themselves, which cmpc_batch_evaluate alone needs, are read from the handle's snapshot
+// of the caller's rows: launch_evaluate's inst_rows.)
+struct KInst {
+  KModel mdl;
+  float mu_inv;    // 1.f / (float) mu, as KParams::mu_inv
+  float f_max;     // (float) f_max
+  float pad[2];
+};
+static_assert(sizeof(KInst) == 64 && offsetof(KInst, mdl) == 0, "one 64-byte entry per instance, KModel first");
+
 // Kernel-side copy of cmpc_params (by value, lands in SGPRs).
 struct KParams {
   float dt;
@@ -50,6 +65,9 @@ struct KParams {
   // the step's fp64 powers for that refinement (scalar registers, not per-lane conversions)
   double dt64, dth64, dt3_64;  // dt, dt^2 / 2, dt^3 / 6
   KModel mdl;      // the handle's robot model (cmpc_batch_set_model)
+  // the per-instance table (cmpc_batch_set_instance_params): entry i replaces mdl, mu_inv and f_max
+  // for instance i; null when no table is set. Last, so no other field's offset depends on it
+  const KInst* inst;
 };
 
 // Kernel-side copy of cmpc_loco_params + the handle's horizon / record stride.
@@ -173,7 +191,8 @@ constexpr int kGaussTaps = 2 * kGaussR7 + 1 + 2 * kGaussR27 + 1;
 hipError_t launch_estimate(float* d_est, const float* d_logs, const float* d_fext3,
                            const float* d_time, float sim_time, float* d_records, int rec_words,
                            float* d_fext6, const float* d_gauss, int batch, hipStream_t stream,
-                           const KModel& mdl, float* d_fest_out = nullptr, const uint8_t* d_due = nullptr);
+                           const KModel& mdl, float* d_fest_out = nullptr, const uint8_t* d_due = nullptr,
+                           const KInst* inst = nullptr);  // inst: entry i's model for instance i's residual
 // batched input assembly (cmpc_assemble.hip): one control tick per instance
 hipError_t launch_assemble(float* d_loco, const LocoParams& lp, float* d_recs, uint8_t* d_due,
                            int batch, hipStream_t stream);
@@ -183,7 +202,7 @@ hipError_t launch_expand(const float* d_compact, float* d_recs, int batch, int N
 // single-rigid-body step of every due instance with its solved step-0 forces (cmpc_assemble.hip)
 hipError_t launch_rollout(float* d_loco, const float* d_recs, const float* d_forces,
                           const float* d_xi6, const uint8_t* d_due, const LocoParams& lp, float dt,
-                          const KModel& mdl, int batch, hipStream_t stream);
+                          const KModel& mdl, int batch, hipStream_t stream, const KInst* inst = nullptr);
 // parity hook and JCQP condensation: full (nothing eliminated) qH [12N x 12N] / qg [12N] per
 // instance (cmpc_condense.hip)
 hipError_t launch_condense(const float* d_recs, int batch, const KParams& P, float* d_H, float* d_g, bool rows,
@@ -191,10 +210,18 @@ hipError_t launch_condense(const float* d_recs, int batch, const KParams& P, flo
 // fp64 prediction, cost and optimality gap of given forces [batch x 12N] (cmpc_evaluate.hip), one
 // wavefront per instance; alpha = the force regularisation (KParams holds 2 alpha in fp32 only).
 // ib64 = the body inertia's three doubles (KParams holds their reciprocals only).
-// d_xpred / d_cert: either may be NULL
+// d_xpred / d_cert: either may be NULL. With P.inst, inst_rows = the handle's snapshot of the
+// caller's rows (CMPC_INST_WORDS doubles each): instance i's inertia doubles come from row i
 hipError_t launch_evaluate(const float* d_recs, const float* d_forces, int batch, const KParams& P,
                            double alpha, const double* ib64, float* d_xpred, double* d_cert,
-                           hipStream_t stream);
+                           hipStream_t stream, const double* inst_rows = nullptr);
+// per-instance table (cmpc_launch.hip). check: *d_bad += the number of rows that
+// cmpc_batch_set_model or cmpc_batch_set_params would refuse (d_bad zeroed by the caller);
+// convert: the kernel-side entries and the snapshot of the rows, formed as make_kmodel and
+// make_kparams form the handle's values on the host
+hipError_t launch_inst_check(const double* d_rows, int count, int* d_bad, hipStream_t stream);
+hipError_t launch_inst_convert(const double* d_rows, int count, KInst* d_entries, double* d_snapshot,
+                               hipStream_t stream);
 
 // use_jcqp == 1 / 2: batched JCQP ADMM over the full / reduced condensed QP (cmpc_admm.hip).
 // Instances whose QP has n > 120 variables run on nslabs persistent workgroups with M in

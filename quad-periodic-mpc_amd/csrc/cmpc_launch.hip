@@ -24,7 +24,8 @@ namespace {
 // DUE (cmpc_batch_solve_due): a thread whose instance is not due classifies nothing and reads no
 // record word; cnt[kHdrBatch] counts the due instances and cnt[kHdrCall] holds the whole batch. The
 // unmasked kernel below is the DUE = false body under its unchanged signature.
-template <bool DUE>
+// INST (a handle with a per-instance table): instance i's own f_max, from its table entry.
+template <bool DUE, bool INST = false>
 __device__ __forceinline__ void classify_body(const float* __restrict__ recs, const uint8_t* __restrict__ due,
                                               int batch, const KParams& P, int* __restrict__ cnt,
                                               int* __restrict__ lists, int max_batch, int c1_max,
@@ -51,12 +52,14 @@ __device__ __forceinline__ void classify_body(const float* __restrict__ recs, co
     const uint32_t* g =
         reinterpret_cast<const uint32_t*>(recs + (size_t)i * P.rec_words + CMPC_REC_GAIT(P.N));
     int nfs = 0;
+    float f_max = P.f_max;
+    if constexpr (INST) f_max = P.inst[i].f_max;
     for (int k = 0; k < P.N; k++) {
       const uint32_t w = g[k];
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         // eliminated iff |gait * f_max| < 0.01, exactly as the solver kernels test it
-        const float ub = (float)((w >> (8 * j)) & 0xffu) * P.f_max;
+        const float ub = (float)((w >> (8 * j)) & 0xffu) * f_max;
         nfs += (ub < 0.01f && ub > -0.01f) ? 0 : 1;
       }
     }
@@ -107,6 +110,29 @@ __global__ __launch_bounds__(64) void cmpc_classify_due_kernel(const float* __re
                       (1u << kLists) - 1u, 1);
 }
 
+// the two kernels above for a handle with a per-instance table (kernels of their own names: the
+// shared ones keep theirs and their registers)
+__global__ __launch_bounds__(64) void cmpc_classify_inst_kernel(const float* __restrict__ recs, int batch,
+                                                                KParams P, int* __restrict__ cnt,
+                                                                int* __restrict__ lists, int max_batch,
+                                                                int c1_max, int* __restrict__ next_hdr,
+                                                                int c1_listed, int tail,
+                                                                int* __restrict__ host_hint,
+                                                                unsigned list_mask, int header_duty) {
+  classify_body<false, true>(recs, nullptr, batch, P, cnt, lists, max_batch, c1_max, next_hdr, c1_listed, tail,
+                             host_hint, list_mask, header_duty);
+}
+
+__global__ __launch_bounds__(64) void cmpc_classify_due_inst_kernel(const float* __restrict__ recs,
+                                                                    const uint8_t* __restrict__ due, int batch,
+                                                                    KParams P, int* __restrict__ cnt,
+                                                                    int* __restrict__ lists, int max_batch,
+                                                                    int c1_max, int* __restrict__ next_hdr,
+                                                                    int tail, int* __restrict__ host_hint) {
+  classify_body<true, true>(recs, due, batch, P, cnt, lists, max_batch, c1_max, next_hdr, 1, tail, host_hint,
+                            (1u << kLists) - 1u, 1);
+}
+
 // Launch form of the wide class holding n in [lo, hi] (cmpc_wide.h): one workgroup per list entry
 // for the populous classes, persistent workgroups for the sparse ones. Populous: the class meets
 // 6N +- 3 sqrt(N), the trot size (two feet in stance at every step) +- one standard deviation of n
@@ -155,6 +181,10 @@ hipError_t launch_solve(const float* d_recs, int batch, const KParams& P, float*
   // lists on the side streams as below. Everything here that does not test `due` is the unmasked
   // sequence.
   const bool due = d_due != nullptr;
+  // a handle with a per-instance table: the classify kernels that read each instance's own f_max
+  // (every solver launcher below picks its per-instance build by P.inst itself)
+  const auto classify_k = P.inst ? cmpc_classify_inst_kernel : cmpc_classify_kernel;
+  const auto classify_due_k = P.inst ? cmpc_classify_due_inst_kernel : cmpc_classify_due_kernel;
   int* cnt = d_work + ctx.hdr * kHdr;             // zero: zeroed at create or by the last classify
   int* next_hdr = d_work + (ctx.hdr ^ 1) * kHdr;  // the next solve's, zeroed by this one's classify
   int* list[kLists];
@@ -209,7 +239,7 @@ hipError_t launch_solve(const float* d_recs, int batch, const KParams& P, float*
   // waiting for class-1 waves to retire
   static const int tself_env = diag_knob("CMPC_TAIL_SELF", 0);
   static const int tself_chunk = diag_knob("CMPC_TAIL_SELF_CHUNK", 64);
-  const bool tail_self = tself_env > 0 && tail_on && tself_chunk >= 1 && tself_chunk <= 64 && !due;
+  const bool tail_self = tself_env > 0 && !P.inst && tail_on && tself_chunk >= 1 && tself_chunk <= 64 && !due;
   const int t8_pos = tail_self ? -1 : (t8_env >= 0) ? t8_env : ((batch >= 131072 && !wide_first) ? 1 : 2);
   // side streams forked and joined by this solve (the third only for the tail class's own chain)
   const int nsides = (tail && (t8_pos == 2 || tail_self)) ? 3 : 2;
@@ -239,7 +269,7 @@ hipError_t launch_solve(const float* d_recs, int batch, const KParams& P, float*
   if (due && n_max <= 64) {
     // the horizons whose unmasked solve needs no classify pass (every n <= 60): the due form lists
     // the due instances (all in list 5) and class 1 runs over that list; no side stream is used
-    hipLaunchKernelGGL(cmpc_classify_due_kernel, dim3((batch + 63) / 64), dim3(64), 0, stream, d_recs, d_due,
+    hipLaunchKernelGGL(classify_due_k, dim3((batch + 63) / 64), dim3(64), 0, stream, d_recs, d_due,
                        batch, P, cnt, d_work + 2 * kHdr, max_batch, c1_nv, next_hdr, 0, ctx.d_hint);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     ctx.last_hdr = ctx.hdr;
@@ -301,16 +331,16 @@ hipError_t launch_solve(const float* d_recs, int batch, const KParams& P, float*
       for (int s = 1; s < 3; s++)
         if ((e = hipStreamWaitEvent(ctx.side[s], ctx.fork, 0)) != hipSuccess) return e;
     if (due)
-      hipLaunchKernelGGL(cmpc_classify_due_kernel, dim3((batch + 63) / 64), dim3(64), 0, cs, d_recs, d_due,
+      hipLaunchKernelGGL(classify_due_k, dim3((batch + 63) / 64), dim3(64), 0, cs, d_recs, d_due,
                          batch, P, cnt, d_work + 2 * kHdr, max_batch, c1_nv, next_hdr, tail ? 1 : 0, ctx.d_hint);
     else
-      hipLaunchKernelGGL(cmpc_classify_kernel, dim3((batch + 63) / 64), dim3(64), 0, cs,
+      hipLaunchKernelGGL(classify_k, dim3((batch + 63) / 64), dim3(64), 0, cs,
                          d_recs, batch, P, cnt, d_work + 2 * kHdr, max_batch, c1_nv, next_hdr, c1_list_mode ? 1 : 0,
                          tail ? 1 : 0, ctx.d_hint, per_side ? m0 : all_lists, 1);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if (per_side)
       for (int s = 1; s < 3; s++) {
-        hipLaunchKernelGGL(cmpc_classify_kernel, dim3((batch + 63) / 64), dim3(64), 0, ctx.side[s],
+        hipLaunchKernelGGL(classify_k, dim3((batch + 63) / 64), dim3(64), 0, ctx.side[s],
                            d_recs, batch, P, cnt, d_work + 2 * kHdr, max_batch, c1_nv, next_hdr, 0,
                            tail ? 1 : 0, nullptr, s == 1 ? m1 : m2, 0);
         if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -489,6 +519,91 @@ hipError_t launch_solve(const float* d_recs, int batch, const KParams& P, float*
   }
   if (ev) (void)hipEventRecord(ev[2], stream);
   return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The per-instance table (cmpc_batch_set_instance_params): rows of CMPC_INST_WORDS doubles ->
+// entries of KInst. Both kernels one thread per row. The derived values are the expressions of
+// make_kmodel and make_kparams (cmpc_abi.cpp) in the same order and types; this unit is compiled
+// with the flags of every other one (IEEE division in both precisions, fp32 denormals kept), so a
+// row equal to a handle's model and parameters gives that handle's bits.
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+__device__ __forceinline__ KInst inst_from_row(const double* __restrict__ row) {
+  KInst e;
+  const double mass = row[CMPC_INST_MASS];
+#pragma unroll
+  for (int i = 0; i < 3; i++) {
+    const double ib = row[CMPC_INST_INERTIA + i];
+    e.mdl.ib[i] = (float)ib;
+    e.mdl.iinv64[i] = 1.0 / ib;
+  }
+  e.mdl.im = 1.f / (float)mass;
+  e.mdl.im64 = 1.0 / mass;
+  e.mu_inv = 1.f / (float)row[CMPC_INST_MU];
+  e.f_max = (float)row[CMPC_INST_FMAX];
+  e.pad[0] = 0.f;
+  e.pad[1] = 0.f;
+  return e;
+}
+
+__device__ __forceinline__ bool fin64(double v) { return v == v && fabs(v) <= 1.7976931348623157e308; }
+__device__ __forceinline__ bool fin32(float v) { return v == v && fabsf(v) <= 3.402823466e38f; }
+
+// a row cmpc_batch_set_model (model_ok) or the table's own rules for mu and f_max refuse
+__device__ __forceinline__ bool inst_row_bad(const double* __restrict__ row) {
+  bool ok = true;
+#pragma unroll
+  for (int w = 0; w < CMPC_INST_WORDS; w++) ok = ok && fin64(row[w]);
+  // mass and inertia: finite and positive, in double and after the fp32 kernels' cast ...
+#pragma unroll
+  for (int w = CMPC_INST_MASS; w < CMPC_INST_INERTIA + 3; w++)
+    ok = ok && row[w] > 0.0 && fin32((float)row[w]) && (float)row[w] > 0.f;
+  // ... and every value derived from them (a denormal mass or inertia has an infinite reciprocal)
+  const KInst e = inst_from_row(row);
+  ok = ok && fin32(e.mdl.im) && e.mdl.im > 0.f && fin64(e.mdl.im64) && e.mdl.im64 > 0.0;
+#pragma unroll
+  for (int i = 0; i < 3; i++) ok = ok && fin64(e.mdl.iinv64[i]) && e.mdl.iinv64[i] > 0.0;
+  // mu: positive, with a finite positive fp32 reciprocal (fmat's 1 / mu); f_max: finite in fp32
+  // (zero and below the elimination threshold are legal: every foot-step of the instance swings)
+  ok = ok && row[CMPC_INST_MU] > 0.0 && fin32(e.mu_inv) && e.mu_inv > 0.f && fin32(e.f_max);
+  return !ok;
+}
+
+__global__ __launch_bounds__(256) void cmpc_inst_check_kernel(const double* __restrict__ rows, int count,
+                                                              int* __restrict__ bad) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const bool b = i < count && inst_row_bad(rows + (size_t)i * CMPC_INST_WORDS);
+  const unsigned long long m = __ballot(b);
+  if ((threadIdx.x & 63) == 0 && m) atomicAdd(bad, __popcll(m));
+}
+
+__global__ __launch_bounds__(256) void cmpc_inst_convert_kernel(const double* __restrict__ rows, int count,
+                                                                KInst* __restrict__ entries,
+                                                                double* __restrict__ snapshot) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= count) return;
+  const double* row = rows + (size_t)i * CMPC_INST_WORDS;
+  entries[i] = inst_from_row(row);
+#pragma unroll
+  for (int w = 0; w < CMPC_INST_WORDS; w++) snapshot[(size_t)i * CMPC_INST_WORDS + w] = row[w];
+}
+
+}  // namespace
+
+hipError_t launch_inst_check(const double* d_rows, int count, int* d_bad, hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(cmpc_inst_check_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, d_rows, count, d_bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_inst_convert(const double* d_rows, int count, KInst* d_entries, double* d_snapshot,
+                               hipStream_t stream) {
+  if (count <= 0) return hipSuccess;
+  hipLaunchKernelGGL(cmpc_inst_convert_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, d_rows, count,
+                     d_entries, d_snapshot);
+  return hipGetLastError();
 }
 
 // One instance whose reduced size n the caller already knows (counted on the host from the

@@ -172,7 +172,9 @@ __device__ __forceinline__ float group_sum(float v) {
 
 // POFF: byte offset of the kernel's KParams argument in its argument segment (make_model reads the
 // model's values there, late)
-template <int T, int POFF>
+// INST: the per-instance build (cmpc_batch_set_instance_params): the model, f_max and 1 / mu from
+// the instance's table entry P.inst[inst] (scalar loads, inst_late) instead
+template <int T, int POFF, bool INST = false>
 __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KParams& P,
                                         SharedT<T>& sh, float* __restrict__ fout,
                                         uint8_t* __restrict__ st_out, int32_t* __restrict__ it_out,
@@ -201,12 +203,14 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
   const unsigned char* gait = reinterpret_cast<const unsigned char*>(srec + CMPC_REC_HDR + 12 * N);
   int nfs = 0;
   unsigned long long msk0 = 0ull, msk1 = 0ull;
+  float f_max = P.f_max;
+  if constexpr (INST) f_max = inst_late<float>(inst_entry(P, inst), kInstFmaxOff);
   for (int c0 = 0; c0 < 4 * N; c0 += 64) {
     const int t = c0 + v;
     float ub = 0.f;
     bool f = false;
     if (t < 4 * N) {
-      ub = (float)gait[t] * P.f_max;
+      ub = (float)gait[t] * f_max;
       f = !(ub < 0.01f && ub > -0.01f);
     }
     const unsigned long long m = __ballot(f);
@@ -242,7 +246,8 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
   }
   if (v < nfs) sh.cmask[v] = 0;
   Model md;
-  make_model<POFF + (int)offsetof(KParams, mdl)>(srec, P.dt, P.mdl, md);
+  if constexpr (INST) make_model<kModelFromInst>(srec, P.dt, P.mdl, md, inst_entry(P, inst));
+  else make_model<POFF + (int)offsetof(KParams, mdl)>(srec, P.dt, P.mdl, md);
   make_bdt<64>(srec, md, v, sh.u.BdtT);
   tsync();
   if (v < N) {
@@ -658,7 +663,8 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
   T_MARK(5);
   // ---- Goldfarb-Idnani dual active set on the friction pyramids (class 1's loop; the tail
   // rows' parts beside every row operation)
-  const float mui = P.mu_inv;
+  float mui = P.mu_inv;
+  if constexpr (INST) mui = inst_late<float>(inst_entry(P, inst), kInstMuInvOff);
   const float fnorm = rsqrtf(mui * mui + 1.f);
   int q = 0;
   int iters = 0;
@@ -1041,6 +1047,42 @@ __global__ __launch_bounds__(64, CMPC_TAIL_WAVES_PER_EU) void cmpc_solve_t_rest_
   }
 }
 
+// The per-instance builds of the two kernels above (solve_t's INST): kernels of their own names, so
+// the shared builds keep theirs and their registers.
+__global__ __launch_bounds__(64, CMPC_TAIL_WAVES_PER_EU) void cmpc_solve_t_inst_kernel(
+    const float* __restrict__ recs, KParams P, float* __restrict__ forces, uint8_t* __restrict__ status,
+    int32_t* __restrict__ iters, const int* __restrict__ in_list, const int* __restrict__ in_count,
+    int* __restrict__ ovf_list, int* __restrict__ ovf_count, int first) {
+  using KP = KArg<1, decltype(&cmpc_solve_t_inst_kernel)>;
+  static_assert(std::is_same<KP::type, KParams>::value, "argument 1 is the KParams");
+  __shared__ SharedT<kTailRows> sh;
+#if CMPC_TAIL_PRIO > 0
+  __builtin_amdgcn_s_setprio(CMPC_TAIL_PRIO);
+#endif
+  const int b = first + (int)blockIdx.x;
+  if (b >= *in_count) return;
+  const int t = in_list[b];
+  solve_t<kTailRows, KP::offset(), true>(recs + (size_t)t * P.rec_words, P, sh, forces + (size_t)t * P.out_cols,
+                                         status + t, iters ? iters + t : nullptr, ovf_list, ovf_count, t);
+}
+
+__global__ __launch_bounds__(64, CMPC_TAIL_WAVES_PER_EU) void cmpc_solve_t_rest_inst_kernel(
+    const float* __restrict__ recs, KParams P, float* __restrict__ forces, uint8_t* __restrict__ status,
+    int32_t* __restrict__ iters, const int* __restrict__ in_list, const int* __restrict__ in_count,
+    int* __restrict__ ovf_list, int* __restrict__ ovf_count, int first) {
+  using KP = KArg<1, decltype(&cmpc_solve_t_rest_inst_kernel)>;
+  static_assert(std::is_same<KP::type, KParams>::value, "argument 1 is the KParams");
+  __shared__ SharedT<kTailRows> sh;
+  const int count = *in_count;
+  for (int b = first + (int)blockIdx.x; b < count; b += (int)gridDim.x) {
+    const int t = in_list[b];
+    solve_t<kTailRows, KP::offset(), true>(recs + (size_t)t * P.rec_words, P, sh, forces + (size_t)t * P.out_cols,
+                                           status + t, iters ? iters + t : nullptr, ovf_list, ovf_count, t);
+    __builtin_amdgcn_wave_barrier();
+    asm volatile("" ::: "memory");
+  }
+}
+
 // Self-classifying form (no classify list, so it can start ahead of class 1 instead of behind the
 // classify pass): workgroup g scans chunks g, g + G, ... of `chunk` instances, lanes < chunk count
 // the stance foot-steps of one instance each (the classify pass's test: eliminated iff
@@ -1099,6 +1141,14 @@ hipError_t launch_tail(const float* d_recs, const KParams& P, float* d_forces, u
                        int32_t* d_iters, const int* in_list, const int* in_count, int* ovf_list,
                        int* ovf_count, int grid, hipStream_t stream, int rest_grid) {
   if (grid <= 0) return hipSuccess;
+  if (P.inst) {  // the per-instance builds
+    hipLaunchKernelGGL(cmpc_solve_t_inst_kernel, dim3(grid), dim3(64), 0, stream, d_recs, P, d_forces, d_status,
+                       d_iters, in_list, in_count, ovf_list, ovf_count, 0);
+    if (rest_grid > 0)
+      hipLaunchKernelGGL(cmpc_solve_t_rest_inst_kernel, dim3(rest_grid), dim3(64), 0, stream, d_recs, P, d_forces,
+                         d_status, d_iters, in_list, in_count, ovf_list, ovf_count, grid);
+    return hipGetLastError();
+  }
   hipLaunchKernelGGL(cmpc_solve_t_kernel, dim3(grid), dim3(64), 0, stream, d_recs, P, d_forces, d_status, d_iters,
                      in_list, in_count, ovf_list, ovf_count, 0);
   if (rest_grid > 0)

@@ -298,9 +298,11 @@ constexpr int kWideMdlOff = (int)(offsetof(WideArgs, P) + offsetof(KParams, mdl)
 // 1 / m in phases B and D of the refinement: the grouped load's value, held across the phases. The
 // 256-column build alone re-reads it at each use: at its 256-VGPR cap, holding it cost 20 B of
 // scratch per lane
-template <int NV>
-__device__ __forceinline__ double ref_im64(double grouped) {
-  if constexpr (NV > 192 && !CMPC_WIDE_LITERAL) return karg_late<double>(kWideMdlOff + (int)offsetof(KModel, im64));
+// (INST, the per-instance build: the same re-read from the instance's table entry ie)
+template <int NV, bool INST = false>
+__device__ __forceinline__ double ref_im64(double grouped, const KInst* ie = nullptr) {
+  if constexpr (NV > 192 && INST) return inst_late<double>(ie, kInstIm64Off);
+  else if constexpr (NV > 192 && !CMPC_WIDE_LITERAL) return karg_late<double>(kWideMdlOff + (int)offsetof(KModel, im64));
   else return grouped;
 }
 
@@ -334,9 +336,10 @@ __device__ __forceinline__ double ref_im64(double grouped) {
 // Phases A-D of wide_refine: the exact QP's gradient at x (xs[] in LDS) into the refinement
 // scratch (24 + 12 N doubles in the R^-1 area). (Out of line, the call saved 95 VGPRs of the J
 // rows around it: N = 16 10.0 -> 8.8 M QP/s, abr2.)
-template <int NV>
+// INST (the per-instance build): the model's fp64 values come from the instance's table entry ie.
+template <int NV, bool INST = false>
 __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in, const KParams& P,
-                                                     SharedW<NV>& sh, int wave) {
+                                                     SharedW<NV>& sh, int wave, const KInst* ie = nullptr) {
   using G = WGeo<NV>;
   constexpr int S0 = 24;  // [0..8] R, [9..17] I_w^-1, [18] x_drag, [19] f_est term, [20] x0[12], [21..23] rpy
   // an opaque record pointer keeps its loads (and the arithmetic on them) from being hoisted out
@@ -359,7 +362,9 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
 #if CMPC_WIDE_LITERAL
   const double ii0 = 1.0 / 0.07, ii1 = 1.0 / 0.26, ii2 = 1.0 / 0.242, im64 = 1.0 / 12.0;
 #else
-  const kf64x4 m64 = karg_late<kf64x4>(kWideMdlOff + (int)offsetof(KModel, iinv64));
+  kf64x4 m64;
+  if constexpr (INST) m64 = inst_late<kf64x4>(ie, kInstIinv64Off);
+  else m64 = karg_late<kf64x4>(kWideMdlOff + (int)offsetof(KModel, iinv64));
   const double ii0 = m64.x, ii1 = m64.y, ii2 = m64.z, im64 = m64.w;  // 1 / I_body, 1 / m
 #endif
   const float* xs = sh.xs();
@@ -462,7 +467,7 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
         const double* ts = scr + S0 + 12 * k;
         const double xd = scr[18];
         // w = B_c u_k (+ Q_c f: f_est(3) into row 9)
-        const double w9 = ts[3] * ref_im64<NV>(im64) + scr[19];
+        const double w9 = ts[3] * ref_im64<NV, INST>(im64, ie) + scr[19];
         double c;
         if (j < 3 || (j >= 6 && j < 9)) {
           // j < 3: dt^2/2 (R' w[6:9])_j; 6..8: dt w_j, w[6:9] = I_w^-1 t
@@ -475,11 +480,11 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
         } else if (j == 3 || j == 9) {
           c = ((j == 3) ? dth : dt) * w9;
         } else if (j == 4 || j == 10) {
-          c = ((j == 4) ? dth : dt) * ts[4] * ref_im64<NV>(im64);
+          c = ((j == 4) ? dth : dt) * ts[4] * ref_im64<NV, INST>(im64, ie);
         } else if (j == 5) {
-          c = dth * ts[5] * ref_im64<NV>(im64) + dt3 * xd * w9;
+          c = dth * ts[5] * ref_im64<NV, INST>(im64, ie) + dt3 * xd * w9;
         } else {
-          c = dt * ts[5] * ref_im64<NV>(im64) + dth * xd * w9;
+          c = dt * ts[5] * ref_im64<NV, INST>(im64, ie) + dth * xd * w9;
         }
         // X_d,k-1 (x0 for k = 0: [rpy, p, w, v], rpy as quat_to_rpy in fp32)
         auto vprev = [&](int i) -> double {
@@ -568,7 +573,7 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
         // fp64 operands were the refining builds' register peak and spilled the J rows' neighbours)
         const int ic = (i < 3) ? i : 0, il = (i < 3) ? 0 : i - 3;
         const double x3 = (i == 3) ? xd : 0.0;
-        const double e2 = (dt * mu[9 + il] + dth * (mu[3 + il] + x3 * mu[11]) + dt3 * x3 * mu[5]) * ref_im64<NV>(im64);
+        const double e2 = (dt * mu[9 + il] + dth * (mu[3 + il] + x3 * mu[11]) + dt3 * x3 * mu[5]) * ref_im64<NV, INST>(im64, ie);
         __builtin_amdgcn_sched_barrier(0);
         double e1 = 0.0;
 #pragma unroll
@@ -586,11 +591,11 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
             ev += Ii[3 * i + m] * nu;
           }
         } else if (i == 3) {
-          ev = (dt * mu[9] + dth * (mu[3] + xd * mu[11]) + dt3 * xd * mu[5]) * ref_im64<NV>(im64);
+          ev = (dt * mu[9] + dth * (mu[3] + xd * mu[11]) + dt3 * xd * mu[5]) * ref_im64<NV, INST>(im64, ie);
         } else if (i == 4) {
-          ev = (dt * mu[10] + dth * mu[4]) * ref_im64<NV>(im64);
+          ev = (dt * mu[10] + dth * mu[4]) * ref_im64<NV, INST>(im64, ie);
         } else {
-          ev = (dt * mu[11] + dth * mu[5]) * ref_im64<NV>(im64);
+          ev = (dt * mu[11] + dth * mu[5]) * ref_im64<NV, INST>(im64, ie);
         }
       }
     }
@@ -600,16 +605,17 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
   wbar();
 }
 
-template <int NV>
+template <int NV, bool INST = false>
 __device__ __forceinline__ void wide_refine(const float* __restrict__ rec_in, const KParams& P, SharedW<NV>& sh,
-                                            float (&slot)[WGeo<NV>::NH], float& xv, int q, int n, int wave) {
+                                            float (&slot)[WGeo<NV>::NH], float& xv, int q, int n, int wave,
+                                            const KInst* ie = nullptr) {
   using G = WGeo<NV>;
   constexpr int NH = G::NH;
   constexpr int NC = (NH + 63) / 64;
   const gfloat* rec = (const gfloat*)(rec_in);
   asm volatile("" : "+s"(rec));
   double* scr = reinterpret_cast<double*>(&sh.P[G::O_RINV]);
-  refine_residual<NV>(rec_in, P, sh, wave);
+  refine_residual<NV, INST>(rec_in, P, sh, wave, ie);
   // ---- E: row r's gradient entry, u = J2' r, x -= J2 u
   float rr = 0.f;
   {
@@ -694,10 +700,14 @@ __device__ __forceinline__ void wide_refine(const float* __restrict__ rec_in, co
   }
 }
 
-template <int NV, bool REFINE>
+// INST: the per-instance build (cmpc_batch_set_instance_params). ie = the instance's table entry
+// (uniform over the workgroup): the model, f_max and 1 / mu come from it by scalar loads (inst_late),
+// each where the shared build reads its own value, instead of P.mdl, P.f_max and P.mu_inv.
+template <int NV, bool REFINE, bool INST = false>
 __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KParams& P,
                                         SharedW<NV>& sh, float* __restrict__ fout,
-                                        uint8_t* __restrict__ st_out, int32_t* __restrict__ it_out) {
+                                        uint8_t* __restrict__ st_out, int32_t* __restrict__ it_out,
+                                        const KInst* ie = nullptr) {
   using G = WGeo<NV>;
   constexpr int NH = G::NH;
   constexpr int RQ = G::RQ;
@@ -720,12 +730,14 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
   const unsigned char* gait = reinterpret_cast<const unsigned char*>(srec + CMPC_REC_HDR + 12 * N);
   int nfs = 0;
   unsigned long long msk0 = 0ull, msk1 = 0ull;
+  float f_max = P.f_max;
+  if constexpr (INST) f_max = inst_late<float>(ie, kInstFmaxOff);
   for (int c0 = 0; c0 < 4 * N; c0 += 64) {
     const int s = c0 + lane;
     float ub = 0.f;
     bool f = false;
     if (s < 4 * N) {
-      ub = (float)gait[s] * P.f_max;
+      ub = (float)gait[s] * f_max;
       f = !(ub < 0.01f && ub > -0.01f);
       if (wave == 0) sh.stance[s] = f ? 1 : 0;
     }
@@ -766,7 +778,8 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
   constexpr KModel kLit{{.07f, 0.26f, 0.242f}, 1.f / 12.0f, {1.0 / 0.07, 1.0 / 0.26, 1.0 / 0.242}, 1.0 / 12.0};
   make_model(srec, P.dt, kLit, md);
 #else
-  make_model<kWideMdlOff>(srec, P.dt, P.mdl, md);
+  if constexpr (INST) make_model<kModelFromInst>(srec, P.dt, P.mdl, md, ie);
+  else make_model<kWideMdlOff>(srec, P.dt, P.mdl, md);
 #endif
   make_bdt<G::NT>(srec, md, t, sh.BdtT());
   wbar();
@@ -1059,7 +1072,8 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
 
   // ---- Goldfarb-Idnani dual active set on the friction pyramids, J's columns relabelled
   // l = h NH + j. One flat loop, one active-set step per trip; R in P, maintained by wave 0
-  const float mui = P.mu_inv;
+  float mui = P.mu_inv;
+  if constexpr (INST) mui = inst_late<float>(ie, kInstMuInvOff);
   const float fnorm = rsqrtf(mui * mui + 1.f);
   int q = 0;
   bool rinv_ok = true;  // R^-1 kept beside R (wave-uniform)
@@ -1494,7 +1508,7 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
     rinv_ok = false;  // the R^-1 area is the refinement's scratch from here on
     it_refined = iters;
     passes++;
-    wide_refine<NV>(rec, P, sh, slot, xv, q, n, wave);
+    wide_refine<NV, INST>(rec, P, sh, slot, xv, q, n, wave, ie);
    }
   }
 
@@ -1525,7 +1539,9 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
       float out = xv;
       if ((z0 || c5) && (c0 || c1) && (c2 || c3)) {
         const float fz = z0 ? 0.f : sh.sub[fs];
-        const float fxy = wdiv(vopq(fz), sopq(P.mu_inv));  // +-mui f + fz = 0 on an active face
+        float mu_inv = P.mu_inv;
+        if constexpr (INST) mu_inv = inst_late<float>(ie, kInstMuInvOff);
+        const float fxy = wdiv(vopq(fz), sopq(mu_inv));  // +-mui f + fz = 0 on an active face
         const bool neg = (ax == 0) ? c0 : c2;
         out = (ax == 2) ? fz : (z0 ? 0.f : (neg ? -fxy : fxy));
       }
@@ -1605,12 +1621,56 @@ __global__ __launch_bounds__(WGeo<NV>::NT, CMPC_WIDE_WAVES_PER_EU) CMPC_WIDE_VGP
   }
 }
 
+// The per-instance build of the kernel above (solve_w's INST; cmpc_batch_set_instance_params): the
+// same two launch forms with the instance's table entry handed to the solve. A kernel of its own
+// name, so the shared build keeps its name and its registers; not built in the literal-model units,
+// which a handle with a table never launches (the host clears KParams::mdl_default).
+#if !CMPC_WIDE_LITERAL
 template <int NV, bool PERSIST, bool REFINE>
+__global__ __launch_bounds__(WGeo<NV>::NT, CMPC_WIDE_WAVES_PER_EU) CMPC_WIDE_VGPR_ATTR void cmpc_solve_w_inst_kernel(
+    WideArgs A) {
+  __shared__ SharedW<NV> sh;
+#if CMPC_WIDE_PRIO > 0
+  __builtin_amdgcn_s_setprio(CMPC_WIDE_PRIO);
+#endif
+  const int count = *A.in_count;
+  if constexpr (!PERSIST) {
+    const int b = blockIdx.x;
+    if (b >= count) return;
+    const int inst = A.in_list[b];
+    solve_w<NV, REFINE, true>(A.recs + (size_t)inst * A.P.rec_words, A.P, sh, A.forces + (size_t)inst * A.P.out_cols,
+                              A.status + inst, A.iters ? A.iters + inst : nullptr, inst_entry(A.P, inst));
+  } else {
+    for (int round = 0;; round++) {
+      if (threadIdx.x == 0) sh.deq_b = A.base + (A.deq ? atomicAdd(A.deq, 1) : (round == 0 ? (int)blockIdx.x : count));
+      wbar();
+      const int b = __builtin_amdgcn_readfirstlane(sh.deq_b);
+      if (b >= count) break;
+      const int inst = A.in_list[b];
+      solve_w<NV, REFINE, true>(A.recs + (size_t)inst * A.P.rec_words, A.P, sh,
+                                A.forces + (size_t)inst * A.P.out_cols, A.status + inst,
+                                A.iters ? A.iters + inst : nullptr, inst_entry(A.P, inst));
+      wbar();
+    }
+  }
+}
+#endif
+
+// (INST: the grid cap of the per-instance build, whose occupancy may differ)
+template <int NV, bool PERSIST, bool REFINE, bool INST = false>
 int wide_grid_cap() {
   static const int cap = [] {
     int nb = 0, dev = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, cmpc_solve_w_kernel<NV, PERSIST, REFINE>, WGeo<NV>::NT,
-                                                     0) != hipSuccess ||
+    hipError_t oe;
+#if !CMPC_WIDE_LITERAL
+    if constexpr (INST)
+      oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, cmpc_solve_w_inst_kernel<NV, PERSIST, REFINE>,
+                                                        WGeo<NV>::NT, 0);
+    else
+#endif
+      oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, cmpc_solve_w_kernel<NV, PERSIST, REFINE>, WGeo<NV>::NT,
+                                                        0);
+    if (oe != hipSuccess ||
         nb <= 0)
       nb = 1;
     if (hipGetDevice(&dev) != hipSuccess ||
@@ -1634,6 +1694,23 @@ hipError_t launch_wide_impl(const float* d_recs, const KParams& P, float* d_forc
   constexpr bool kOne = (CMPC_WIDE_BUILD & 1) != 0, kPersist = (CMPC_WIDE_BUILD & 2) != 0;
   const bool persist = kPersist && (deq != nullptr || !kOne);
   WideArgs A{d_recs, d_forces, d_status, d_iters, in_list, in_count, persist ? deq : nullptr, P, base};
+#if !CMPC_WIDE_LITERAL
+  if (P.inst) {  // the per-instance builds, in the same two launch forms
+    constexpr bool kRef = CMPC_WIDE_REFINE != 0;
+    if (persist) {
+      if constexpr (kPersist) {
+        if (deq) grid = grid < wide_grid_cap<NV, true, kRef, true>() ? grid : wide_grid_cap<NV, true, kRef, true>();
+        hipLaunchKernelGGL((cmpc_solve_w_inst_kernel<NV, true, kRef>), dim3(grid), dim3(WGeo<NV>::NT), 0, stream, A);
+      }
+    } else {
+      if constexpr (kOne)
+        hipLaunchKernelGGL((cmpc_solve_w_inst_kernel<NV, false, kRef>), dim3(grid), dim3(WGeo<NV>::NT), 0, stream, A);
+    }
+    return hipGetLastError();
+  }
+#else
+  if (P.inst) return hipErrorInvalidValue;  // a literal-model build is never taken while a table is set
+#endif
   if (persist) {
     if constexpr (kPersist) {
       constexpr bool kRef = CMPC_WIDE_REFINE != 0;

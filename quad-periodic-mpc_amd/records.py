@@ -118,6 +118,33 @@ def make_model(mass: float = DEFAULT_MASS, inertia=DEFAULT_INERTIA) -> CmpcModel
     return m
 
 
+# Per-instance table rows (include/cmpc_solver.h CMPC_INST_*): float64 words
+INST_MASS, INST_INERTIA, INST_MU, INST_FMAX, INST_WORDS = 0, 1, 4, 5, 6
+
+
+def make_instance_params(mass=DEFAULT_MASS, inertia=DEFAULT_INERTIA, mu=0.4, f_max=120.0) -> np.ndarray:
+    """Rows of the per-instance table (``BatchSolver.set_instance_params``): ``mass`` [B] (kg),
+    ``inertia`` [B, 3] (Ixx, Iyy, Izz, kg m^2), ``mu`` [B] and ``f_max`` [B] (N), each broadcast
+    against the others (scalars and one row of inertia included), as a float64 ``[B, 6]`` array in
+    the order mass, Ixx, Iyy, Izz, mu, f_max. The defaults are the default robot on the reference's
+    ground (mu = 0.4, f_max = 120)."""
+    mass = np.asarray(mass, np.float64)
+    inertia = np.asarray(inertia, np.float64)
+    mu = np.asarray(mu, np.float64)
+    f_max = np.asarray(f_max, np.float64)
+    if inertia.ndim == 0 or inertia.shape[-1] != 3 or inertia.ndim > 2:
+        raise ValueError("inertia takes the three principal moments (Ixx, Iyy, Izz) per row")
+    if mass.ndim > 1 or mu.ndim > 1 or f_max.ndim > 1:
+        raise ValueError("mass, mu and f_max are scalars or [B] arrays")
+    b = np.broadcast_shapes(mass.shape or (1,), inertia.shape[:-1] or (1,), mu.shape or (1,), f_max.shape or (1,))
+    out = np.empty(b + (INST_WORDS,), np.float64)
+    out[:, INST_MASS] = mass
+    out[:, INST_INERTIA:INST_INERTIA + 3] = inertia
+    out[:, INST_MU] = mu
+    out[:, INST_FMAX] = f_max
+    return out
+
+
 # ConvexMPCLocomotion.cpp:617 (Q), :623 (alpha), :807 (mu = 0.4, f_max = 120); dtMPC = 0.002 * 13
 DEFAULT_WEIGHTS = (0.25, 0.25, 10, 10, 2, 50, 0, 0, 0.3, 0.2, 0.2, 0.1)
 

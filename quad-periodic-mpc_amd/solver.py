@@ -20,6 +20,7 @@ import os
 import numpy as np
 
 from .records import CmpcModel, CmpcParams, LocoParams, make_model, make_params, record_words
+from .records import INST_WORDS, make_instance_params  # noqa: F401
 from .records import (CERT_COST, CERT_COST0, CERT_GAP, CERT_VIOL, CERT_SWING, CERT_GRADMAX,  # noqa: F401
                       CERT_WORDS, MAX_HORIZON)
 
@@ -40,6 +41,7 @@ EXPORTED_SYMBOLS = (
     "cmpc_batch_evaluate", "cmpc_batch_evaluate_host", "cmpc_evaluate_last",
     "cmpc_batch_solve_due", "cmpc_batch_estimate_due",
     "cmpc_batch_set_model", "cmpc_batch_get_model", "cmpc_set_model",
+    "cmpc_batch_set_instance_params", "cmpc_batch_instance_count",
     "cmpc_batch_quadprog",   # include/cmpc_quadprog.h
 )
 
@@ -139,6 +141,9 @@ def load_library(path: str = LIB_PATH):
         lib.cmpc_batch_set_model.argtypes = [ctypes.c_void_p, ctypes.POINTER(CmpcModel)]
         lib.cmpc_batch_get_model.argtypes = [ctypes.c_void_p, ctypes.POINTER(CmpcModel)]
         lib.cmpc_set_model.argtypes = [ctypes.POINTER(CmpcModel)]
+    if hasattr(lib, "cmpc_batch_set_instance_params"):  # (A/B libraries built before the table lack it)
+        lib.cmpc_batch_set_instance_params.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        lib.cmpc_batch_instance_count.argtypes = [ctypes.c_void_p]
     lib.cmpc_batch_quadprog.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int] + \
         [ctypes.c_void_p] * 7 + [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int]
     _lib = lib
@@ -260,7 +265,7 @@ class BatchSolver:
     """Reentrant batched solver bound to one HIP stream (``cmpc_batch_*``)."""
 
     def __init__(self, params: CmpcParams | None = None, max_batch: int = 65536, stream=None,
-                 horizon: int = 10, model: CmpcModel | None = None):
+                 horizon: int = 10, model: CmpcModel | None = None, instance_params=None):
         self.lib = load_library()
         self.params = params if params is not None else make_params(horizon)
         self.max_batch = int(max_batch)
@@ -277,9 +282,12 @@ class BatchSolver:
         _check(self.lib.cmpc_batch_create(ctypes.byref(h), ctypes.byref(self.params),
                                           self.max_batch, s), "cmpc_batch_create")
         self._h = h
-        if model is not None:
+        if model is not None or instance_params is not None:
             try:
-                self.set_model(model)
+                if model is not None:
+                    self.set_model(model)
+                if instance_params is not None:
+                    self.set_instance_params(instance_params)
             except Exception:
                 self.close()
                 raise
@@ -301,6 +309,39 @@ class BatchSolver:
         m = CmpcModel()
         _check(self.lib.cmpc_batch_get_model(self._h, ctypes.byref(m)), "cmpc_batch_get_model")
         return m
+
+    def set_instance_params(self, table) -> None:
+        """Per-instance mass, inertia, friction coefficient and force limit
+        (``cmpc_batch_set_instance_params``): ``table`` is ``[B, 6]`` float64, rows of
+        (mass, Ixx, Iyy, Izz, mu, f_max) as :func:`make_instance_params` builds them, either a numpy
+        array (uploaded here) or a float64 CUDA tensor; row i belongs to instance i of every later
+        call. The library snapshots the rows; ``None`` clears the table (the handle's shared model,
+        mu and f_max again). A bad row raises (-2) and leaves the previous table, or none, in force."""
+        if not hasattr(self.lib, "cmpc_batch_set_instance_params"):
+            raise CmpcError("this libcmpc_hip.so has no cmpc_batch_set_instance_params")
+        if table is None:
+            _check(self.lib.cmpc_batch_set_instance_params(self._h, None, 0), "cmpc_batch_set_instance_params")
+            return
+        import torch
+        if hasattr(table, "data_ptr"):
+            if table.dtype != torch.float64 or not table.is_cuda:
+                raise CmpcError("set_instance_params: a tensor table must be float64 on the device")
+            dev = table
+        else:
+            dev = torch.from_numpy(np.ascontiguousarray(table, np.float64)).cuda()
+        if dev.dim() != 2 or dev.shape[1] != INST_WORDS or not dev.is_contiguous():
+            raise CmpcError(f"set_instance_params: the table must be contiguous [B, {INST_WORDS}], "
+                            f"got {tuple(dev.shape)}")
+        torch.cuda.current_stream().synchronize()  # the upload, or the caller's writes, before the snapshot
+        _check(self.lib.cmpc_batch_set_instance_params(self._h, dev.data_ptr(), int(dev.shape[0])),
+               "cmpc_batch_set_instance_params")
+
+    @property
+    def instance_count(self) -> int:
+        """Rows of the per-instance table in force (``cmpc_batch_instance_count``; 0: none set)."""
+        if not hasattr(self.lib, "cmpc_batch_instance_count"):
+            return 0
+        return int(self.lib.cmpc_batch_instance_count(self._h))
 
     @property
     def horizon(self) -> int:
