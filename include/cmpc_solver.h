@@ -147,13 +147,30 @@ typedef struct cmpc_loco_params {
 
 /* Per-instance status (batched API). The reference has no status: on qpOASES failure it prints
  * "failed to solve!" and leaves stale forces (SolverMPC.cpp:964-968). Documented deviation:
- * forces are zero when status != CMPC_OK. */
+ * every force of the instance is +0.0 when status != CMPC_OK, and an instance with CMPC_OK has
+ * finite forces inside its friction pyramids. A failed instance changes nothing of any other
+ * instance, in the same call or in a later one on the same handle (tests/test_gpu_status.py).
+ *
+ * Non-finite input: a record word that the solve reads (p, v, q, omega, r of a leg with a stance
+ * step, x_drag, the trajectory, f_est(3) while the flag bit is set) and that is NaN, +-Inf or
+ * >= 3e38 in magnitude. Where the word reaches only the gradient (p, v, omega, trajectory,
+ * f_est) the status is CMPC_BAD_INPUT. Where it reaches the Hessian (q, r, x_drag) the NaN meets
+ * a Cholesky pivot first and the status is CMPC_NOT_PD or CMPC_BAD_INPUT: the kernels do not tell
+ * the two apart. Words the solve does not read (the stored roll / pitch / yaw, f_est(3) while the
+ * flag is clear) are without effect. A trajectory row ahead of the record's first stance step
+ * reaches no force: non-finite there, the instance is either solved as if the word were finite
+ * (n <= 64, and 65..72 at N <= 10) or refused with CMPC_BAD_INPUT (the larger size classes).
+ * The shared parameters (cmpc_params) are not validated:
+ * with valid ones, 0 is always feasible and the cap is max_iter + 2n trips (n = reduced
+ * variables), so CMPC_INFEASIBLE and CMPC_MAX_ITER need invalid parameters (f_max < 0) or a
+ * lowered max_iter, and CMPC_NOT_PD needs alpha <= -diag(B'SB) or non-finite input. */
 enum {
   CMPC_OK = 0,
-  CMPC_MAX_ITER = 1,      /* active-set iteration cap (reference nWSR = 100) reached          */
+  CMPC_MAX_ITER = 1,      /* more than max_iter + 2n active-set trips (reference nWSR = 100)   */
   CMPC_INFEASIBLE = 2,    /* friction-pyramid QP infeasible                                    */
-  CMPC_NOT_PD = 3,        /* Hessian factorisation failed                                      */
-  CMPC_BAD_INPUT = 4      /* horizon out of range / non-finite input                           */
+  CMPC_NOT_PD = 3,        /* Hessian factorisation failed (a pivot <= 0 or NaN)                */
+  CMPC_BAD_INPUT = 4      /* non-finite input that left the Hessian finite: the solution would */
+                          /* not be a number (horizon out of range is refused by the host API) */
 };
 
 /* Batch-shared problem parameters (problem_setup + the update_data_t scalars that the caller

@@ -335,6 +335,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
     for (int t = v; t < (P.rec_words >> 2); t += 64) dst[t] = src[t];
   }
   lsync();
+  refuse_bad_words<64>(&sh.P[OFF_REC], N, v);  // (ordered ahead of make_model by the lsync below)
   const float* srec = &sh.P[OFF_REC];
   const KInst* ie = nullptr;  // this instance's table entry (uniform)
   float f_max = P.f_max;
@@ -1261,6 +1262,10 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
 
   C1_MARK(4);
   // ---- scatter (q_soln layout 12 k + 3 leg + axis, swing -> 0) staged in LDS, coalesced out
+  // A solution that is no number is refused: a non-finite record word that reaches only the
+  // gradient leaves every pivot positive, and a NaN never wins a comparison of the violation scan,
+  // so the loop above ends "optimal" on it.
+  if (status == CMPC_OK && __ballot(v < n && !result_is_number(xv)) != 0ull) status = CMPC_BAD_INPUT;
   const bool ok = (status == CMPC_OK);
   if constexpr (OOFF >= 0) {
     fout = karg_late<float*>(OOFF) + (size_t)inst * P.out_cols;

@@ -23,6 +23,36 @@ namespace {
 constexpr int MAXN = CMPC_MAX_HORIZON;
 constexpr float kBigF = 3.0e38f;
 
+// The failure contract's input side (include/cmpc_solver.h CMPC_BAD_INPUT), run by the NT threads
+// of the workgroup over the LDS copy of a horizon-N record, between the barrier that completes the
+// copy and the one ahead of the first read of a float word (the stance scan in between reads gait
+// bytes only). A float word that is no number the solve can compute with (NaN, +-Inf,
+// |x| >= kBigF) becomes a quiet NaN, so that a huge finite word cannot overflow its way back to a
+// plausible number. From there it either meets a Cholesky pivot (CMPC_NOT_PD) or, through the
+// gradient alone, makes the whole solution NaN, which result_is_number refuses where the forces
+// are written out. The flag word and its pad (bit patterns) and the gait bytes stay as they are; a
+// word the solve never reads stays without effect. Nothing is stored for a record of finite words.
+__device__ __forceinline__ float word_or_nan(float x) { return (fabsf(x) < kBigF) ? x : __builtin_nanf(""); }
+template <int NT>
+__device__ __forceinline__ void refuse_bad_words(float* srec, int N, int tid) {
+  static_assert(CMPC_REC_FLAGS % 4 == 2 && CMPC_REC_HDR % 4 == 0, "the flag word and its pad end a float4");
+  float4* s4 = reinterpret_cast<float4*>(srec);
+  for (int i = tid; i < ((CMPC_REC_HDR + 12 * N) >> 2); i += NT) {
+    const float4 x = s4[i];
+    float4 y = x;
+    y.x = word_or_nan(x.x);
+    y.y = word_or_nan(x.y);
+    if (i != (CMPC_REC_FLAGS >> 2)) {
+      y.z = word_or_nan(x.z);
+      y.w = word_or_nan(x.w);
+    }
+    // (y differs from x only where a word was replaced: a NaN compares unequal to itself too)
+    if (!(y.x == x.x && y.y == x.y && y.z == x.z && y.w == x.w)) s4[i] = y;
+  }
+}
+// The output side: is this force a number? (false for NaN, +-Inf and anything from kBigF up)
+__device__ __forceinline__ bool result_is_number(float x) { return fabsf(x) < kBigF; }
+
 // ---------------------------------------------------------------------------------------------
 // wavefront helpers. Reductions use DPP lane permutes inside the VALU (row permutes, then the
 // row_bcast15 / row_bcast31 steps across the four 16-lane rows) and hand back a wave-uniform

@@ -198,6 +198,7 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
     for (int t = v; t < (P.rec_words >> 2); t += 64) dst[t] = src[t];
   }
   tsync();
+  refuse_bad_words<64>(&sh.P[T_OFF_REC], N, v);  // (ordered ahead of make_model by the tsync below)
   const float* srec = &sh.P[T_OFF_REC];
   // ---- stance table + elimination (SolverMPC.cpp:869-894)
   const unsigned char* gait = reinterpret_cast<const unsigned char*>(srec + CMPC_REC_HDR + 12 * N);
@@ -977,6 +978,10 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
   }
 
   // ---- scatter (q_soln layout 12 k + 3 leg + axis, swing -> 0) staged in LDS, coalesced out
+  // a solution that is no number is refused (class 1's rule; every lane holds a variable, n > 64)
+  if (status == CMPC_OK &&
+      __ballot(!result_is_number(xv) || (ts == 0 && 64 + ti < n && !result_is_number(xt))) != 0ull)
+    status = CMPC_BAD_INPUT;
   const bool ok = (status == CMPC_OK);
   tsync();
   for (int t = v; t < 12 * N; t += 64) sh.P[t] = 0.f;

@@ -725,6 +725,7 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
     for (int i = t; i < (P.rec_words >> 2); i += G::NT) dst[i] = src[i];
   }
   wbar();
+  refuse_bad_words<G::NT>(&sh.P[W_OFF_REC], N, t);  // (ordered ahead of make_model by the barrier below)
   const float* srec = &sh.P[W_OFF_REC];
   // ---- stance table + elimination (SolverMPC.cpp:869-894); every wave compacts, wave 0 stores
   const unsigned char* gait = reinterpret_cast<const unsigned char*>(srec + CMPC_REC_HDR + 12 * N);
@@ -798,6 +799,13 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
   // place, M1 / M2 in ZE
   moment_recur(&sh.P[W_OFF_E], &sh.P[W_OFF_ZE], N, tid_opq());
   wbar();
+  // The failure contract's check of the wide classes (class 1 and the tail class test x at their
+  // scatter; here that cost the refining builds scratch). Every record word that
+  // reaches only the gradient enters through the weighted state errors, and M0 of step 0 is
+  // their sum over all steps: a word there that is no number refuses the instance
+  // (CMPC_BAD_INPUT, the loop is skipped, zero forces). Every wave reads the same thirteen
+  // words behind the barrier above, so the verdict is uniform over the workgroup.
+  const bool g_bad = __ballot(!result_is_number(sh.P[W_OFF_E + ((lane_opq() < 13) ? lane_opq() : 0)])) != 0ull;
 
   // ---- condensation: row r's lanes build H[r][w], w >= r (half h takes every other w of a
   // block), into packed upper rows of P; both compute the gradient g_r
@@ -868,7 +876,7 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
 
   // ---- bordered Cholesky [H | g]: pivot column k = register k/2 of half k%2 of every row,
   // published into P's row k (even / odd segments), one s_barrier per step
-  int status = CMPC_OK;
+  int status = g_bad ? (int)CMPC_BAD_INPUT : (int)CMPC_OK;
   float my_inv = 1.f;
 #if CMPC_DIAG_STOP != 3  // diagnostic build 3: stop after the condensation and the H-row load
 #if CMPC_WIDE_CHOL2
