@@ -269,7 +269,8 @@ CMPC_EXTERNC int cmpc_batch_get_model(const cmpc_batch* h, cmpc_model* out);
 /* d_inst: device pointer to count * CMPC_INST_WORDS doubles, 1 <= count <= max_batch. Row i belongs
  * to instance i of every later call: the index of its record, with or without a due mask. The call
  * snapshots the rows (later writes to d_inst have no effect until the next call) into a
- * handle-owned table of kernel-side values, one 64-byte entry per instance, derived by the
+ * handle-owned table of kernel-side values, the first 64-byte line of an entry per instance
+ * (the second line is cmpc_batch_set_instance_costs'), derived by the
  * expressions the handle's own model and parameters go through ((float) inertia, 1.f / (float)
  * mass, 1.0 / inertia, 1.0 / mass, 1.f / (float) mu, (float) f_max), so a row equal to a handle's
  * model, mu and f_max gives that handle's bits; beside it the rows themselves (48 bytes per
@@ -288,11 +289,49 @@ CMPC_EXTERNC int cmpc_batch_get_model(const cmpc_batch* h, cmpc_model* out);
  * |gait x f_max| < 0.01 eliminates every foot-step of that instance alone. Each of these calls with
  * batch > count returns its bad-arguments error and writes nothing. cmpc_batch_get_model still
  * returns the handle's shared model; cmpc_batch_set_model and _set_params still work and the table
- * survives both: their model, mu and f_max become visible again when the table is cleared. dt,
- * weights, alpha, horizon, max_iter, refine and output steps stay batch-shared. The single-instance
+ * survives both: their model, mu and f_max become visible again when the table is cleared. The
+ * weights and alpha have a table of their own (cmpc_batch_set_instance_costs below); dt, horizon,
+ * max_iter, refine and output steps stay batch-shared. The single-instance
  * surface and libcmpc_multi.so take no table. */
 CMPC_EXTERNC int cmpc_batch_set_instance_params(cmpc_batch* h, const double* d_inst, int count);
 CMPC_EXTERNC int cmpc_batch_instance_count(const cmpc_batch* h);   /* 0: none set */
+/* Per-instance cost: one row of CMPC_COST_WORDS floats per instance, the twelve state weights and the
+ * force regularisation alpha (many candidate costs tuned in one batch, gait-dependent weights in a
+ * mixed batch). The reference takes both on every update_problem_data call and so does the
+ * single-instance surface here; this call gives the batched surface the same freedom. New API. */
+#define CMPC_COST_WEIGHTS 0    /* 12 fp32 state weights, each finite and >= 0 (cmpc_params.weights) */
+#define CMPC_COST_ALPHA   12   /* fp32, finite, > 0, 2.f * alpha finite                              */
+#define CMPC_COST_WORDS   16   /* words 13..15 reserved: never read, any bit pattern                 */
+/* d_cost: device pointer to count * CMPC_COST_WORDS floats, 1 <= count <= max_batch. Row i belongs
+ * to instance i of every later call: the index of its record, with or without a due mask. The call
+ * snapshots the rows (later writes to d_cost have no effect until the next call) into the second
+ * 64-byte line of the handle-owned table of kernel-side entries (128 bytes per instance: the first
+ * line is cmpc_batch_set_instance_params'), 2.f * alpha formed by the expression the handle's own
+ * alpha goes through, so a row equal to a handle's weights and alpha gives that handle's bits. The
+ * table's buffers are allocated for max_batch instances by the first call of either table (make it
+ * outside stream capture) and freed by cmpc_batch_destroy; no solve allocates. A set-up call: it
+ * synchronises the handle's stream (a validation kernel counts the bad rows, the host reads the
+ * count, a conversion kernel fills the table).
+ * A row is bad when a weight is negative or non-finite, when alpha is non-finite or <= 0, or when
+ * 2.f * alpha is not finite. (cmpc_params itself validates none of these; the table is stricter
+ * because a bad alpha in one row would otherwise show only as that instance's CMPC_NOT_PD.) With
+ * any bad row the call returns -2 and the handle keeps its previous table, or none. d_cost == NULL
+ * clears the table: the handle is then bit for bit the handle it was before (shared weights, alpha).
+ * While a table is set, instance i uses row i in place of the handle's weights and alpha in
+ * cmpc_batch_solve, _solve_due, _solve_host, _condense, _condense_rows and _evaluate(_host);
+ * _admm follows through the H and g it is given; _rollout, _estimate(_due), _assemble and _expand
+ * read neither value. Each call that takes a batch returns its bad-arguments error and writes
+ * nothing when batch > count.
+ * The cost table and the parameter table are independent: either, both or neither may be set, in
+ * any order, and each is cleared on its own; with both set, batch must not exceed either count.
+ * Both survive cmpc_batch_set_params and cmpc_batch_set_model; of the shared values a table does
+ * not cover, the newest apply to every instance (with only a cost table, a later set_model or a new
+ * mu reaches every row; with only a parameter table, new shared weights do), refreshed by a kernel
+ * on the handle's stream without allocation or host synchronisation.
+ * Out of scope: per-instance dt, horizon and max_iter; the single-instance surface, which already
+ * takes weights and alpha per call; libcmpc_multi.so and parallel.RootPipeline. */
+CMPC_EXTERNC int cmpc_batch_set_instance_costs(cmpc_batch* h, const float* d_cost, int count);
+CMPC_EXTERNC int cmpc_batch_instance_cost_count(const cmpc_batch* h);   /* 0: none set */
 /* Device-resident solve: d_records [batch * cmpc_record_words(N)] fp32, d_forces
  * [batch * 12N] fp32 (step-major, leg*3+axis), d_status [batch] uint8, d_iters [batch] int32
  * (may be NULL). Asynchronous on the handle's stream. Returns 0 or a negative error. */

@@ -2,5 +2,5 @@
 from .records import (CmpcModel, make_model, CmpcParams, make_params, pack_records, record_words, unpack_gait,  # noqa: F401
                       DEFAULT_WEIGHTS, STATUS_NAMES, CERT_COST, CERT_COST0, CERT_GAP, CERT_VIOL,
                       CERT_SWING, CERT_GRADMAX, CERT_WORDS, make_instance_params, INST_MASS, INST_INERTIA,
-                      INST_MU, INST_FMAX, INST_WORDS)
+                      INST_MU, INST_FMAX, INST_WORDS, make_instance_costs, COST_WEIGHTS, COST_ALPHA, COST_WORDS)
 from .instances import make_disturbance, make_instances, make_logs, trot_table  # noqa: F401

@@ -46,7 +46,9 @@ struct cmpc_batch {
   cmpc::KInst* d_inst = nullptr;
   double* d_inst_rows = nullptr;
   int* d_inst_bad = nullptr;
-  int inst_count = 0;            // rows of the table in force (0: none, kp.inst is null)
+  int inst_count = 0;            // rows of the parameter table in force (0: none)
+  int cost_count = 0;            // rows of the cost table in force (cmpc_batch_set_instance_costs; 0: none)
+                                 // (kp.inst is null when both are 0)
   double* d_admm_slabs = nullptr;  // ADMM inverses of QPs with n > 120 (cmpc_admm.hip)
   size_t admm_slab_doubles = 0;
   int admm_nslabs = 0;
@@ -222,16 +224,48 @@ static int ensure_admm_slabs(cmpc_batch* h) {
   return 0;
 }
 
-// kp's view of the per-instance table, after anything that rebuilt kp or changed the table. While a
-// table is set no launcher takes a literal-model build (they hold the default robot's values).
-static void apply_inst(cmpc_batch* h) {
-  h->kp.inst = h->inst_count > 0 ? h->d_inst : nullptr;
+// kp's view of the per-instance tables, after anything that rebuilt kp or changed a table. While
+// either is set no launcher takes a literal-model build (they hold the default robot's values).
+// With one of the two set, the other half of its entries takes the handle's shared values as they
+// now stand: a kernel on the handle's stream, behind every earlier call and ahead of every later
+// one, no allocation, no host synchronisation.
+static int apply_inst(cmpc_batch* h) {
+  h->kp.inst = (h->inst_count > 0 || h->cost_count > 0) ? h->d_inst : nullptr;
   h->kp.mdl_default = !h->kp.inst && std::memcmp(&h->model, &kDefaultModel, sizeof h->model) == 0;
+  if (!h->kp.inst || (h->inst_count > 0 && h->cost_count > 0)) return 0;
+  const bool model_half = h->inst_count == 0;
+  const hipError_t e =
+      cmpc::launch_inst_fill(h->d_inst, h->d_inst_rows, model_half ? h->cost_count : h->inst_count, model_half,
+                             h->kp, h->model, (double)h->prm.mu, (double)h->prm.f_max, h->prm.alpha, h->stream);
+  if (e != hipSuccess) return fail("launch_inst_fill", e);
+  return 0;
 }
 
 // a batch the handle can take: within max_batch and, with a per-instance table, within its rows
 static bool batch_ok(const cmpc_batch* h, int batch) {
-  return batch >= 0 && batch <= h->max_batch && (h->inst_count == 0 || batch <= h->inst_count);
+  return batch >= 0 && batch <= h->max_batch && (h->inst_count == 0 || batch <= h->inst_count) &&
+         (h->cost_count == 0 || batch <= h->cost_count);
+}
+
+// the tables' buffers, for max_batch, by the first call that sets either table: 128 B of entry and
+// 48 B of row snapshot per instance, and the validation kernels' counter
+static int ensure_inst_buffers(cmpc_batch* h) {
+  if (h->d_inst) return 0;
+  hipError_t e;
+  cmpc::KInst* ent = nullptr;
+  double* rows = nullptr;
+  int* bad = nullptr;
+  if ((e = hipMalloc(&ent, sizeof(cmpc::KInst) * (size_t)h->max_batch)) != hipSuccess ||
+      (e = hipMalloc(&rows, sizeof(double) * CMPC_INST_WORDS * (size_t)h->max_batch)) != hipSuccess ||
+      (e = hipMalloc(&bad, sizeof(int))) != hipSuccess) {
+    if (ent) (void)hipFree(ent);
+    if (rows) (void)hipFree(rows);
+    return fail("hipMalloc(instance table)", e);
+  }
+  h->d_inst = ent;
+  h->d_inst_rows = rows;
+  h->d_inst_bad = bad;
+  return 0;
 }
 
 extern "C" int cmpc_batch_set_params(cmpc_batch* h, const cmpc_params* prm) {
@@ -244,7 +278,7 @@ extern "C" int cmpc_batch_set_params(cmpc_batch* h, const cmpc_params* prm) {
   h->kp = make_kparams(*prm, h->model);
   if (h->out_steps > 0 && h->out_steps < prm->horizon) h->kp.out_cols = 12 * h->out_steps;
   if (!h->refine) h->kp.refine = 0;
-  apply_inst(h);
+  if (int r = apply_inst(h)) return r;
   return ensure_admm_slabs(h);
 }
 
@@ -257,8 +291,7 @@ extern "C" int cmpc_batch_set_model(cmpc_batch* h, const cmpc_model* m) {
   }
   h->model = nm;
   h->kp.mdl = make_kmodel(nm);
-  apply_inst(h);
-  return 0;
+  return apply_inst(h);
 }
 
 extern "C" int cmpc_batch_set_instance_params(cmpc_batch* h, const double* d_inst, int count) {
@@ -267,28 +300,15 @@ extern "C" int cmpc_batch_set_instance_params(cmpc_batch* h, const double* d_ins
   if (!d_inst) {  // clear: the shared model, mu and f_max again (the buffers stay for the next table)
     if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
     h->inst_count = 0;
-    apply_inst(h);
+    if (int r = apply_inst(h)) return r;  // (under a cost table: the shared model, mu and f_max into its entries)
+    if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
     return 0;
   }
   if (count < 1 || count > h->max_batch) {
     g_last_error = "cmpc_batch_set_instance_params: count must be in 1..max_batch";
     return -1;
   }
-  if (!h->d_inst) {  // first call: 64 B + 48 B per instance of max_batch
-    cmpc::KInst* ent = nullptr;
-    double* rows = nullptr;
-    int* bad = nullptr;
-    if ((e = hipMalloc(&ent, sizeof(cmpc::KInst) * (size_t)h->max_batch)) != hipSuccess ||
-        (e = hipMalloc(&rows, sizeof(double) * CMPC_INST_WORDS * (size_t)h->max_batch)) != hipSuccess ||
-        (e = hipMalloc(&bad, sizeof(int))) != hipSuccess) {
-      if (ent) (void)hipFree(ent);
-      if (rows) (void)hipFree(rows);
-      return fail("hipMalloc(instance table)", e);
-    }
-    h->d_inst = ent;
-    h->d_inst_rows = rows;
-    h->d_inst_bad = bad;
-  }
+  if (int r = ensure_inst_buffers(h)) return r;  // first call of either table
   int bad = 0;
   if ((e = hipMemsetAsync(h->d_inst_bad, 0, sizeof(int), h->stream)) != hipSuccess) return fail("memset", e);
   if ((e = cmpc::launch_inst_check(d_inst, count, h->d_inst_bad, h->stream)) != hipSuccess)
@@ -304,13 +324,51 @@ extern "C" int cmpc_batch_set_instance_params(cmpc_batch* h, const double* d_ins
   }
   if ((e = cmpc::launch_inst_convert(d_inst, count, h->d_inst, h->d_inst_rows, h->stream)) != hipSuccess)
     return fail("launch_inst_convert", e);
-  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
   h->inst_count = count;
-  apply_inst(h);
+  if (int r = apply_inst(h)) return r;  // (without a cost table: the shared weights and alpha beside the rows)
+  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
   return 0;
 }
 
 extern "C" int cmpc_batch_instance_count(const cmpc_batch* h) { return h ? h->inst_count : 0; }
+
+extern "C" int cmpc_batch_set_instance_costs(cmpc_batch* h, const float* d_cost, int count) {
+  if (!h) return -1;
+  hipError_t e;
+  if (!d_cost) {  // clear: the shared weights and alpha again (the buffers stay for the next table)
+    if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
+    h->cost_count = 0;
+    if (int r = apply_inst(h)) return r;  // (under a parameter table: the shared cost into its entries)
+    if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
+    return 0;
+  }
+  if (count < 1 || count > h->max_batch) {
+    g_last_error = "cmpc_batch_set_instance_costs: count must be in 1..max_batch";
+    return -1;
+  }
+  if (int r = ensure_inst_buffers(h)) return r;  // first call of either table
+  int bad = 0;
+  if ((e = hipMemsetAsync(h->d_inst_bad, 0, sizeof(int), h->stream)) != hipSuccess) return fail("memset", e);
+  if ((e = cmpc::launch_cost_check(d_cost, count, h->d_inst_bad, h->stream)) != hipSuccess)
+    return fail("launch_cost_check", e);
+  if ((e = hipMemcpyAsync(&bad, h->d_inst_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
+    return fail("D2H", e);
+  // (also: every earlier call on the handle's stream that reads the table in force is done)
+  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
+  if (bad != 0) {
+    g_last_error = "cmpc_batch_set_instance_costs: " + std::to_string(bad) +
+                   " bad row(s): weights must be finite and >= 0, alpha finite and > 0 with 2 alpha finite";
+    return -2;
+  }
+  if ((e = cmpc::launch_cost_convert(d_cost, count, h->d_inst, h->stream)) != hipSuccess)
+    return fail("launch_cost_convert", e);
+  h->cost_count = count;
+  if (int r = apply_inst(h)) return r;  // (without a parameter table: the shared model, mu and f_max beside the rows)
+  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
+  return 0;
+}
+
+extern "C" int cmpc_batch_instance_cost_count(const cmpc_batch* h) { return h ? h->cost_count : 0; }
 
 extern "C" int cmpc_batch_get_model(const cmpc_batch* h, cmpc_model* out) {
   if (!h || !out) return -1;
@@ -745,7 +803,7 @@ extern "C" int cmpc_batch_solve_host(cmpc_batch* h, const float* records, int ba
   // one instance (the reference ABI's operating mode): the fast path, unless per-launch timing
   // is on (it brackets the batched launch sequence)
   // (with a per-instance table the batched sequence: its classify pass reads the row's f_max)
-  if (batch == 1 && h->ev_steps == 0 && h->inst_count == 0) return solve_single_host(h, records, forces, status, iters);
+  if (batch == 1 && h->ev_steps == 0 && !h->kp.inst) return solve_single_host(h, records, forces, status, iters);
   hipError_t e;
   if ((e = hipMemcpyAsync(h->d_rec, records, rw * batch * sizeof(float), hipMemcpyHostToDevice, h->stream)) != hipSuccess)
     return fail("H2D", e);

@@ -311,8 +311,9 @@ __device__ __forceinline__ float pick_col(const float (&x)[MA], int q) {
 // then read where the instance is written out (karg_late), not held in six SGPRs from kernel
 // entry, and fout / st_out / it_out are not used.
 // INST: the per-instance build (cmpc_batch_set_instance_params). The instance's table entry
-// P.inst[inst] gives the model, f_max and 1 / mu in place of P.mdl, P.f_max and P.mu_inv: scalar
-// loads at a wave-uniform address (inst_late), each where the shared build first reads its value.
+// P.inst[inst] gives the model, f_max, 1 / mu, the weights and 2 alpha in place of P.mdl, P.f_max,
+// P.mu_inv, P.wts and P.alpha2: scalar loads at a wave-uniform address (inst_late), each where the
+// shared build first reads its value.
 template <int NV, int POFF = -1, int OOFF = -1, bool INST = false>
 __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KParams& P,
                                          SharedC1<NV>& sh, float* __restrict__ fout,
@@ -395,9 +396,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
   make_cond_geo<true>(srec, md, cg);
   lsync();
   float wts[13];
-#pragma unroll
-  for (int j = 0; j < 12; j++) wts[j] = P.wts[j];
-  wts[12] = 0.f;
+  cost_weights<INST>(P, ie, wts);
   if (v < N) {  // the weighted state error we_v = S e_v of step v
     float e[13];
     state_error(srec, md, v, srec + CMPC_REC_HDR + 12 * v, e);
@@ -463,12 +462,21 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
           {
             // the weights re-read from the argument segment (scalar loads) in every step: held
             // from kernel entry they keep twelve SGPRs through the whole stage, which spills
-            const kf32x4 w0 = karg_late<kf32x4>(POFF + (int)offsetof(KParams, wts)),
-                         w1 = karg_late<kf32x4>(POFF + (int)offsetof(KParams, wts) + 16),
-                         w2 = karg_late<kf32x4>(POFF + (int)offsetof(KParams, wts) + 32);
+            // (a per-instance build: from the instance's entry, the same way)
+            kf32x4 w0, w1, w2;
+            if constexpr (INST) {
+              w0 = inst_late<kf32x4>(ie, kInstWtsOff);
+              w1 = inst_late<kf32x4>(ie, kInstWtsOff + 16);
+              w2 = inst_late<kf32x4>(ie, kInstWtsOff + 32);
+            } else {
+              w0 = karg_late<kf32x4>(POFF + (int)offsetof(KParams, wts));
+              w1 = karg_late<kf32x4>(POFF + (int)offsetof(KParams, wts) + 16);
+              w2 = karg_late<kf32x4>(POFF + (int)offsetof(KParams, wts) + 32);
+            }
             const float ws[13] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x, w2.y, w2.z, w2.w, 0.f};
             recur(ms, ws, gk, z);
           }
+          const float alpha2 = cost_alpha2<INST>(P, ie);
           StepProj pj;
           step_proj(ms, cg, z, pj);
           // (the ballot opaque: the step's nibble is shifted out here, not kept from the test above)
@@ -496,7 +504,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
             static_for<0, 3>([&](auto AC) {
               constexpr int c = 6 * i + 3 * s + decltype(AC)::value;
               float x = val[decltype(AC)::value];
-              if (c == v) x += P.alpha2;  // qH = 2 (B'SB + alpha I), SolverMPC.cpp:806
+              if (c == v) x += alpha2;  // qH = 2 (B'SB + alpha I), SolverMPC.cpp:806
               slot[c] = real ? x : ((c == v) ? 1.f : 0.f);
             });
           });
@@ -519,6 +527,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
 #endif
     {
       const int myrow = G::tri(v);
+      const float alpha2 = cost_alpha2<INST>(P, ie);
       for (int i = N - 1; i >= 0; i--) {
         // z_i = S Adt^{i-kv} b_v + Adt' z_{i+1}  (the S term only for i >= kv)
         const bool act = real && (i >= kv);
@@ -532,7 +541,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
         asm volatile("" ::: "memory");  // the step's LDS traffic stays inside the step
         const int wb = __builtin_amdgcn_readfirstlane(sh.blkbase[i]);
         step_entries(md, cg, sh.u.BdtT, step_mask(msk0, msk1, i), wb, z, [&](int w, float val) {
-          if (w == v) val += P.alpha2;  // qH = 2 (B'SB + alpha I), SolverMPC.cpp:806
+          if (w == v) val += alpha2;  // qH = 2 (B'SB + alpha I), SolverMPC.cpp:806
           if (act && w >= v) sh.P[myrow + w] = val;
         });
       }

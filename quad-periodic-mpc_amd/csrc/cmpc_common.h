@@ -564,6 +564,39 @@ constexpr int kInstMuInvOff = (int)offsetof(KInst, mu_inv);
 constexpr int kInstFmaxOff = (int)offsetof(KInst, f_max);
 constexpr int kInstIinv64Off = (int)(offsetof(KInst, mdl) + offsetof(KModel, iinv64));
 constexpr int kInstIm64Off = (int)(offsetof(KInst, mdl) + offsetof(KModel, im64));
+constexpr int kInstWtsOff = (int)offsetof(KInst, wts);
+constexpr int kInstAlpha2Off = (int)offsetof(KInst, alpha2);
+// The cost of a solver build: the shared builds read the handle's weights and 2 alpha from their
+// arguments, as ever; a per-instance build (INST) from the second line of the instance's entry ie.
+template <bool INST>
+__device__ __forceinline__ float cost_alpha2(const KParams& P, const KInst* ie) {
+  if constexpr (INST) return inst_late<float>(ie, kInstAlpha2Off);
+  else return P.alpha2;
+}
+// The unconstrained minimiser's entry x = -(J y)_v from its sum s. A per-instance build takes
+// 0 - s: the same bits for every s but a zero, which comes out +0.0 whatever its sign, so a row
+// whose cost has a zero gradient (twelve zero weights) gives forces of exactly +0.0. The shared
+// builds keep their negation, and write -0.0 there.
+template <bool INST>
+__device__ __forceinline__ float neg_sum(float s) {
+  if constexpr (INST) return 0.f - s;
+  else return -s;
+}
+// (three 16-byte scalar loads; wts[12] = 0: the thirteenth state is the gravity constant)
+template <bool INST>
+__device__ __forceinline__ void cost_weights(const KParams& P, const KInst* ie, float (&wts)[13]) {
+  if constexpr (INST) {
+    const kf32x4 w0 = inst_late<kf32x4>(ie, kInstWtsOff), w1 = inst_late<kf32x4>(ie, kInstWtsOff + 16),
+                 w2 = inst_late<kf32x4>(ie, kInstWtsOff + 32);
+    wts[0] = w0.x; wts[1] = w0.y; wts[2] = w0.z; wts[3] = w0.w;
+    wts[4] = w1.x; wts[5] = w1.y; wts[6] = w1.z; wts[7] = w1.w;
+    wts[8] = w2.x; wts[9] = w2.y; wts[10] = w2.z; wts[11] = w2.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 12; j++) wts[j] = P.wts[j];
+  }
+  wts[12] = 0.f;
+}
 // make_model's MOFF of a per-instance build: the model's fp32 values come from the table entry
 constexpr int kModelFromInst = -2;
 

@@ -95,7 +95,7 @@ __device__ void condense_one(const float* __restrict__ rec, const KParams& P, Sh
 }
 
 #if CMPC_CONDENSE_INST
-// instance i under the model of its table entry: the shared parameters with that entry's model
+// instance i under its table entry: the shared parameters with that entry's model, weights and 2 alpha
 __global__ __launch_bounds__(NTG) void cmpc_condense_inst_kernel(const float* __restrict__ recs, int batch, KParams P,
                                                                  float* __restrict__ Hout, float* __restrict__ gout,
                                                                  int rows) {
@@ -104,6 +104,9 @@ __global__ __launch_bounds__(NTG) void cmpc_condense_inst_kernel(const float* __
   for (int inst = blockIdx.x; inst < batch; inst += gridDim.x) {
     KParams Pi = P;
     Pi.mdl = P.inst[inst].mdl;
+#pragma unroll
+    for (int j = 0; j < 12; j++) Pi.wts[j] = P.inst[inst].wts[j];
+    Pi.alpha2 = P.inst[inst].alpha2;
     condense_one(recs + (size_t)inst * P.rec_words, Pi, sh, Hout + inst * n * n, gout + inst * n, rows != 0);
     __syncthreads();
   }

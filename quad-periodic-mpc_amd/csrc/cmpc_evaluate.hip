@@ -70,10 +70,10 @@ __device__ __forceinline__ double bfly_max(double v) {
 }
 
 // CMPC_EVALUATE_INST = 1 (cmpc_evaluate_inst.hip, which includes this file): the per-instance build
-// for a handle with a table (cmpc_batch_set_instance_params), a kernel and a launcher of their own
+// for a handle with a table (cmpc_batch_set_instance_params, _set_instance_costs), a kernel and a launcher of their own
 // names in a unit of their own, so that this unit compiles the shared kernel exactly as before. The
 // kernel's body is the one below: instance i first takes its inertia doubles from row i of the
-// handle's snapshot of the caller's rows and 1 / m, 1 / mu and f_max from its table entry.
+// handle's snapshot of the rows and 1 / m, 1 / mu, f_max, the weights and alpha from its table entry.
 #if CMPC_EVALUATE_INST
 __global__ __launch_bounds__(64) void cmpc_evaluate_inst_kernel(const float* __restrict__ d_recs,
                                                                 const float* __restrict__ d_forces, int batch,
@@ -91,6 +91,15 @@ __global__ __launch_bounds__(64) void cmpc_evaluate_inst_kernel(const float* __r
     P.mdl.im64 = e->mdl.im64;
     P.mu_inv = e->mu_inv;
     P.f_max = e->f_max;
+    // (the cost by scalar loads, the instance being the workgroup's: the weights stay uniform
+    // values, as the shared kernel's are)
+    const KInst* eu = inst_entry(P, inst);
+    float w[13];
+    cost_weights<true>(P, eu, w);
+#pragma unroll
+    for (int j = 0; j < 12; j++) P.wts[j] = w[j];
+    P.alpha2 = inst_late<float>(eu, kInstAlpha2Off);
+    alpha = inst_late<double>(eu, (int)offsetof(KInst, alpha64));
   }
 #else
 __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restrict__ d_recs,

@@ -33,19 +33,28 @@ struct KModel {
   double im64;       // 1.0 / mass
 };
 
-// One row of a handle's per-instance table (cmpc_batch_set_instance_params): what instance i uses
-// in place of the handle's model, mu and f_max. KModel first, so the fp32 block {ib, im} and the
-// fp64 block {iinv64, im64} sit at the offsets they have in the argument segment's KModel and one
-// scalar load each fetches them; 64 bytes, so an entry never straddles a cache line. (The inertia
-// doubles themselves, which cmpc_batch_evaluate alone needs, are read from the handle's snapshot
-// of the caller's rows: launch_evaluate's inst_rows.)
+// One entry of a handle's per-instance table: what instance i uses in place of the handle's model,
+// mu and f_max (cmpc_batch_set_instance_params: the first 64-byte line) and in place of its weights
+// and alpha (cmpc_batch_set_instance_costs: the second line). KModel first, so the fp32 block
+// {ib, im} and the fp64 block {iinv64, im64} sit at the offsets they have in the argument segment's
+// KModel and one scalar load each fetches them; neither half straddles a cache line. With only one
+// of the two tables set, the other half of every entry holds the handle's shared values
+// (launch_inst_fill). (The inertia doubles themselves, which cmpc_batch_evaluate alone needs, are
+// read from the handle's snapshot of the rows: launch_evaluate's inst_rows.)
 struct KInst {
   KModel mdl;
   float mu_inv;    // 1.f / (float) mu, as KParams::mu_inv
   float f_max;     // (float) f_max
   float pad[2];
+  float wts[12];   // as KParams::wts
+  float alpha2;    // 2.f * alpha, as KParams::alpha2
+  float pad2;
+  double alpha64;  // (double) alpha (cmpc_batch_evaluate's fp64 cost; one scalar load, no conversion)
 };
-static_assert(sizeof(KInst) == 64 && offsetof(KInst, mdl) == 0, "one 64-byte entry per instance, KModel first");
+static_assert(sizeof(KInst) == 128 && offsetof(KInst, mdl) == 0 && offsetof(KInst, mu_inv) == 48 &&
+                  offsetof(KInst, f_max) == 52 && offsetof(KInst, wts) == 64 && offsetof(KInst, alpha2) == 112 &&
+                  offsetof(KInst, alpha64) == 120,
+              "two 64-byte lines per instance: KModel, 1 / mu, f_max; weights, 2 alpha, (double) alpha");
 
 // Kernel-side copy of cmpc_params (by value, lands in SGPRs).
 struct KParams {
@@ -65,8 +74,9 @@ struct KParams {
   // the step's fp64 powers for that refinement (scalar registers, not per-lane conversions)
   double dt64, dth64, dt3_64;  // dt, dt^2 / 2, dt^3 / 6
   KModel mdl;      // the handle's robot model (cmpc_batch_set_model)
-  // the per-instance table (cmpc_batch_set_instance_params): entry i replaces mdl, mu_inv and f_max
-  // for instance i; null when no table is set. Last, so no other field's offset depends on it
+  // the per-instance table (cmpc_batch_set_instance_params, _set_instance_costs): entry i replaces
+  // mdl, mu_inv, f_max, wts and alpha2 for instance i; null when neither table is set. Last, so no
+  // other field's offset depends on it
   const KInst* inst;
 };
 
@@ -208,7 +218,8 @@ hipError_t launch_rollout(float* d_loco, const float* d_recs, const float* d_for
 hipError_t launch_condense(const float* d_recs, int batch, const KParams& P, float* d_H, float* d_g, bool rows,
                            hipStream_t stream);
 // fp64 prediction, cost and optimality gap of given forces [batch x 12N] (cmpc_evaluate.hip), one
-// wavefront per instance; alpha = the force regularisation (KParams holds 2 alpha in fp32 only).
+// wavefront per instance; alpha = the force regularisation (KParams holds 2 alpha in fp32 only;
+// with P.inst, (double) of entry i's alpha instead).
 // ib64 = the body inertia's three doubles (KParams holds their reciprocals only).
 // d_xpred / d_cert: either may be NULL. With P.inst, inst_rows = the handle's snapshot of the
 // caller's rows (CMPC_INST_WORDS doubles each): instance i's inertia doubles come from row i
@@ -222,6 +233,17 @@ hipError_t launch_evaluate(const float* d_recs, const float* d_forces, int batch
 hipError_t launch_inst_check(const double* d_rows, int count, int* d_bad, hipStream_t stream);
 hipError_t launch_inst_convert(const double* d_rows, int count, KInst* d_entries, double* d_snapshot,
                                hipStream_t stream);
+// the cost table (cmpc_batch_set_instance_costs), rows of CMPC_COST_WORDS floats. check: *d_bad +=
+// the number of bad rows (a weight negative or non-finite, alpha non-finite or <= 0, 2.f * alpha
+// not finite); convert: the second line of the entries, alpha2 by make_kparams' expression
+hipError_t launch_cost_check(const float* d_rows, int count, int* d_bad, hipStream_t stream);
+hipError_t launch_cost_convert(const float* d_rows, int count, KInst* d_entries, hipStream_t stream);
+// The half of entries [0, count) that has no table, from the handle's shared values: model = true
+// the first line (P.mdl, P.mu_inv, P.f_max) and the snapshot rows (mdl64, mu, f_max: what a row of
+// cmpc_batch_set_instance_params holds), model = false the second line (P.wts, P.alpha2, alpha).
+// Asynchronous on `stream`, the values by value in the argument segment.
+hipError_t launch_inst_fill(KInst* d_entries, double* d_snapshot, int count, bool model, const KParams& P,
+                            const cmpc_model& mdl64, double mu, double f_max, float alpha, hipStream_t stream);
 
 // use_jcqp == 1 / 2: batched JCQP ADMM over the full / reduced condensed QP (cmpc_admm.hip).
 // Instances whose QP has n > 120 variables run on nslabs persistent workgroups with M in

@@ -170,10 +170,19 @@ __device__ __forceinline__ float group_sum(float v) {
   return v;
 }
 
+// 2 alpha of the diagonal: the shared build's argument, a per-instance build's entry (a scalar
+// load ahead of each of the two condensation loops: nothing of the entry is held past them)
+template <bool INST>
+__device__ __forceinline__ float tail_alpha2(const KParams& P, int inst) {
+  if constexpr (INST) return cost_alpha2<true>(P, inst_entry(P, inst));
+  else return P.alpha2;
+}
+
 // POFF: byte offset of the kernel's KParams argument in its argument segment (make_model reads the
 // model's values there, late)
-// INST: the per-instance build (cmpc_batch_set_instance_params): the model, f_max and 1 / mu from
-// the instance's table entry P.inst[inst] (scalar loads, inst_late) instead
+// INST: the per-instance build (cmpc_batch_set_instance_params, _set_instance_costs): the model,
+// f_max, 1 / mu, the weights and 2 alpha from the instance's table entry P.inst[inst] (scalar
+// loads, inst_late) instead
 template <int T, int POFF, bool INST = false>
 __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KParams& P,
                                         SharedT<T>& sh, float* __restrict__ fout,
@@ -259,9 +268,8 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
   }
   tsync();
   float wts[13];
-#pragma unroll
-  for (int j = 0; j < 12; j++) wts[j] = P.wts[j];
-  wts[12] = 0.f;
+  if constexpr (INST) cost_weights<true>(P, inst_entry(P, inst), wts);
+  else cost_weights<false>(P, nullptr, wts);
   {
     float ze[13];
 #pragma unroll
@@ -311,6 +319,7 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
     }
     tsync();  // every ZE read is issued before P is overwritten
     const int myrow = G::tri(v);
+    const float alpha2 = tail_alpha2<INST>(P, inst);
     float z[13];
 #pragma unroll
     for (int j = 0; j < 13; j++) z[j] = 0.f;
@@ -326,7 +335,7 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
       asm volatile("" ::: "memory");
       const int wb = __builtin_amdgcn_readfirstlane(sh.blkbase[i]);
       step_entries(md, cg, sh.u.BdtT, step_mask(msk0, msk1, i), wb, z, [&](int w, float val) {
-        if (w == v) val += P.alpha2;  // qH = 2 (B'SB + alpha I), SolverMPC.cpp:806
+        if (w == v) val += alpha2;  // qH = 2 (B'SB + alpha I), SolverMPC.cpp:806
         if (act && w >= v) sh.P[myrow + w] = val;
       });
     }
@@ -344,6 +353,7 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
     n1_mul(md, b, u1);
     n1_mul(md, u1, u2);
     const int myrow = G::tri(real ? r : 64);
+    const float alpha2 = tail_alpha2<INST>(P, inst);
     float z[13];
 #pragma unroll
     for (int j = 0; j < 13; j++) z[j] = 0.f;
@@ -359,7 +369,7 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
       asm volatile("" ::: "memory");
       const int wb = __builtin_amdgcn_readfirstlane(sh.blkbase[i]);
       step_entries(md, cg, sh.u.BdtT, step_mask(msk0, msk1, i), wb, z, [&](int w, float val) {
-        if (w == r) val += P.alpha2;
+        if (w == r) val += alpha2;
         if (act && w >= r) sh.P[myrow + w] = val;
       });
     }
@@ -651,13 +661,13 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
         constexpr int c = decltype(C)::value;
         dot4(xacc, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3], y4);
       });
-  float xv = -(xacc.x + xacc.y);
+  float xv = neg_sum<INST>(xacc.x + xacc.y);
   float xt;
   {
     float a = 0.f;
 #pragma unroll
     for (int m = 0; m < SW; m++) a = fmaf(jt[m], sh.vbuf()[SW * ts + m], a);
-    xt = (64 + ti < n) ? -group_sum<LPR>(a) : 0.f;
+    xt = (64 + ti < n) ? neg_sum<INST>(group_sum<LPR>(a)) : 0.f;
   }
   tsync();
 

@@ -520,7 +520,12 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
     const double* R = scr;
     float wf = 0.f;  // P.wts[jj] by uniform selects (a dynamic index would build a VGPR array)
 #pragma unroll
-    for (int i = 0; i < 12; i++) wf = (jj == i) ? P.wts[i] : wf;
+    for (int i = 0; i < 12; i++) {
+      float wi;
+      if constexpr (INST) wi = inst_late<float>(ie, kInstWtsOff + 4 * i);
+      else wi = P.wts[i];
+      wf = (jj == i) ? wi : wf;
+    }
     // forward: z_j += (N1 z)_j + d_k,j   (N1 = Adt - I: rows 0..2 dt R' z[6:9], 3, 4 dt z9, z10,
     // 5 dt z11 + dt^2/2 x_drag z9, 11 dt x_drag z9; z12 = 0)
     double z = 0.0;
@@ -627,7 +632,7 @@ __device__ __forceinline__ void wide_refine(const float* __restrict__ rec_in, co
       const double* yk = scr + 24 + 12 * k;
       // (y x r_b)_a = y_a1 r_a2 - y_a2 r_a1
       const double cr = yk[a1] * (double)rec[CMPC_REC_R + 4 * a2 + b] - yk[a2] * (double)rec[CMPC_REC_R + 4 * a1 + b];
-      rr = (float)(2.0 * (cr + yk[3 + a]) + (double)sopq(P.alpha2) * (double)xv);
+      rr = (float)(2.0 * (cr + yk[3 + a]) + (double)sopq(cost_alpha2<INST>(P, ie)) * (double)xv);
       // A unit vector the foot-step's own working-set rows span (e_z: fz = 0, fz = ub or two
       // opposite faces; with it e_x / e_y from one face of that pair) is a combination of rows of
       // C_W, so J2' annihilates it and the entry does not enter u = J2' r. In fp32 J2's row of such
@@ -701,8 +706,9 @@ __device__ __forceinline__ void wide_refine(const float* __restrict__ rec_in, co
 }
 
 // INST: the per-instance build (cmpc_batch_set_instance_params). ie = the instance's table entry
-// (uniform over the workgroup): the model, f_max and 1 / mu come from it by scalar loads (inst_late),
-// each where the shared build reads its own value, instead of P.mdl, P.f_max and P.mu_inv.
+// (uniform over the workgroup): the model, f_max, 1 / mu, the weights and 2 alpha come from it by
+// scalar loads (inst_late), each where the shared build reads its own value, instead of P.mdl,
+// P.f_max, P.mu_inv, P.wts and P.alpha2.
 template <int NV, bool REFINE, bool INST = false>
 __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KParams& P,
                                         SharedW<NV>& sh, float* __restrict__ fout,
@@ -785,9 +791,7 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
   make_bdt<G::NT>(srec, md, t, sh.BdtT());
   wbar();
   float wts[13];
-#pragma unroll
-  for (int j = 0; j < 12; j++) wts[j] = P.wts[j];
-  wts[12] = 0.f;
+  cost_weights<INST>(P, ie, wts);
   if (t < N) {  // the weighted state error we_t = S e_t of step t
     float e[13];
     state_error(srec, md, t, srec + CMPC_REC_HDR + 12 * t, e);
@@ -828,6 +832,7 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
     float z[13];
 #pragma unroll
     for (int j = 0; j < 13; j++) z[j] = 0.f;
+    const float alpha2 = cost_alpha2<INST>(P, ie);  // (one scalar load, live over the condensation only)
     // (stopping each wavefront below the smallest block of its rows, whose steps build nothing,
     // measured 0.5-1 % slower on every workload: profiles/r03_ab/r03_o)
     for (int i = N - 1; i >= 0; i--) {
@@ -851,7 +856,7 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
 #pragma unroll
         for (int j = 0; j < 13; j++) bw[j] = sh.BdtT()[cw][j];
         float val = 2.f * dot13(bw, z);
-        if (w == r) val += P.alpha2;  // qH = 2 (B'SB + alpha I), SolverMPC.cpp:806
+        if (w == r) val += alpha2;  // qH = 2 (B'SB + alpha I), SolverMPC.cpp:806
         if (act && w < we && w >= r) sh.P[myrow + w] = val;
       }
     }
@@ -1074,7 +1079,7 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
       CMPC_WSWEEP_FENCE(j);
     }
     const float xs2 = pair_sum(xacc.x + xacc.y);
-    xv = (r < n) ? -xs2 : 0.f;
+    xv = (r < n) ? neg_sum<INST>(xs2) : 0.f;
   }
   wbar();  // the factor rows in P are dead from here; P holds R
 

@@ -148,6 +148,28 @@ def make_instance_params(mass=DEFAULT_MASS, inertia=DEFAULT_INERTIA, mu=0.4, f_m
 # ConvexMPCLocomotion.cpp:617 (Q), :623 (alpha), :807 (mu = 0.4, f_max = 120); dtMPC = 0.002 * 13
 DEFAULT_WEIGHTS = (0.25, 0.25, 10, 10, 2, 50, 0, 0, 0.3, 0.2, 0.2, 0.1)
 
+# Per-instance cost table rows (include/cmpc_solver.h CMPC_COST_*): float32 words
+COST_WEIGHTS, COST_ALPHA, COST_WORDS = 0, 12, 16
+
+
+def make_instance_costs(weights=None, alpha=None) -> np.ndarray:
+    """Rows of the per-instance cost table (``BatchSolver.set_instance_costs``): ``weights`` [B, 12]
+    (the state weights, ``cmpc_params.weights``) and ``alpha`` [B] (the force regularisation), each
+    broadcast against the other (one row of weights and a scalar alpha included), as a float32
+    ``[B, 16]`` array: the weights in words 0..11, alpha in word 12, words 13..15 reserved (zero).
+    The defaults are ``DEFAULT_WEIGHTS`` and the reference's 4e-5."""
+    weights = np.asarray(DEFAULT_WEIGHTS if weights is None else weights, np.float32)
+    alpha = np.asarray(4e-5 if alpha is None else alpha, np.float32)
+    if weights.ndim == 0 or weights.shape[-1] != 12 or weights.ndim > 2:
+        raise ValueError("weights takes the twelve state weights per row")
+    if alpha.ndim > 1:
+        raise ValueError("alpha is a scalar or a [B] array")
+    b = np.broadcast_shapes(weights.shape[:-1] or (1,), alpha.shape or (1,))
+    out = np.zeros(b + (COST_WORDS,), np.float32)
+    out[:, COST_WEIGHTS:COST_WEIGHTS + 12] = weights
+    out[:, COST_ALPHA] = alpha
+    return out
+
 
 def make_params(horizon: int = 10, dt: float = 0.026, mu: float = 0.4, f_max: float = 120.0,
                 weights=DEFAULT_WEIGHTS, alpha: float = 4e-5, max_iter: int = 100) -> CmpcParams:

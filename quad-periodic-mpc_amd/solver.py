@@ -21,6 +21,7 @@ import numpy as np
 
 from .records import CmpcModel, CmpcParams, LocoParams, make_model, make_params, record_words
 from .records import INST_WORDS, make_instance_params  # noqa: F401
+from .records import COST_WORDS, make_instance_costs  # noqa: F401
 from .records import (CERT_COST, CERT_COST0, CERT_GAP, CERT_VIOL, CERT_SWING, CERT_GRADMAX,  # noqa: F401
                       CERT_WORDS, MAX_HORIZON)
 
@@ -42,6 +43,7 @@ EXPORTED_SYMBOLS = (
     "cmpc_batch_solve_due", "cmpc_batch_estimate_due",
     "cmpc_batch_set_model", "cmpc_batch_get_model", "cmpc_set_model",
     "cmpc_batch_set_instance_params", "cmpc_batch_instance_count",
+    "cmpc_batch_set_instance_costs", "cmpc_batch_instance_cost_count",
     "cmpc_batch_quadprog",   # include/cmpc_quadprog.h
 )
 
@@ -144,6 +146,9 @@ def load_library(path: str = LIB_PATH):
     if hasattr(lib, "cmpc_batch_set_instance_params"):  # (A/B libraries built before the table lack it)
         lib.cmpc_batch_set_instance_params.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
         lib.cmpc_batch_instance_count.argtypes = [ctypes.c_void_p]
+    if hasattr(lib, "cmpc_batch_set_instance_costs"):  # (likewise)
+        lib.cmpc_batch_set_instance_costs.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
+        lib.cmpc_batch_instance_cost_count.argtypes = [ctypes.c_void_p]
     lib.cmpc_batch_quadprog.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int] + \
         [ctypes.c_void_p] * 7 + [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int]
     _lib = lib
@@ -342,6 +347,38 @@ class BatchSolver:
         if not hasattr(self.lib, "cmpc_batch_instance_count"):
             return 0
         return int(self.lib.cmpc_batch_instance_count(self._h))
+
+    def set_instance_costs(self, table) -> None:
+        """Per-instance state weights and force regularisation (``cmpc_batch_set_instance_costs``):
+        ``table`` is ``[B, 16]`` float32, rows as :func:`make_instance_costs` builds them, either a
+        numpy array (uploaded here) or a float32 CUDA tensor; row i belongs to instance i of every
+        later call. The library snapshots the rows; ``None`` clears the table (the handle's shared
+        weights and alpha again). Independent of :meth:`set_instance_params`. A bad row raises (-2)
+        and leaves the previous table, or none, in force."""
+        if not hasattr(self.lib, "cmpc_batch_set_instance_costs"):
+            raise CmpcError("this libcmpc_hip.so has no cmpc_batch_set_instance_costs")
+        if table is None:
+            _check(self.lib.cmpc_batch_set_instance_costs(self._h, None, 0), "cmpc_batch_set_instance_costs")
+            return
+        import torch
+        if hasattr(table, "data_ptr"):
+            if table.dtype != torch.float32 or not table.is_cuda:
+                raise CmpcError("set_instance_costs: a tensor table must be float32 on the device")
+            dev = table
+        else:
+            dev = torch.from_numpy(np.ascontiguousarray(table, np.float32)).cuda()
+        if dev.dim() != 2 or dev.shape[1] != COST_WORDS or not dev.is_contiguous():
+            raise CmpcError(f"set_instance_costs: the table must be contiguous [B, {COST_WORDS}], "
+                            f"got {tuple(dev.shape)}")
+        torch.cuda.current_stream().synchronize()  # the upload, or the caller's writes, before the snapshot
+        _check(self.lib.cmpc_batch_set_instance_costs(self._h, dev.data_ptr(), int(dev.shape[0])),
+               "cmpc_batch_set_instance_costs")
+
+    def instance_cost_count(self) -> int:
+        """Rows of the cost table in force (``cmpc_batch_instance_cost_count``; 0: none set)."""
+        if not hasattr(self.lib, "cmpc_batch_instance_cost_count"):
+            return 0
+        return int(self.lib.cmpc_batch_instance_cost_count(self._h))
 
     @property
     def horizon(self) -> int:

@@ -1,16 +1,21 @@
-"""What the per-instance table costs: one handle, HIP events around back-to-back
-solves after warm-up, the same records solved two ways in one run:
+"""What the per-instance tables cost: one handle, HIP events around
+back-to-back solves after warm-up, the same records solved in several forms in one run:
 
-  shared   the handle's shared model, mu and f_max (the default robot: the literal builds where
-           there is one);
-  table    a table of identical default rows, one per instance: the per-instance builds, which load
-           each instance's entry, on a problem whose every value is the shared one's.
+  shared   the handle's shared model, mu, f_max, weights and alpha (the default robot: the literal
+           builds where there is one);
+  table    a parameter table (cmpc_batch_set_instance_params) of identical default rows, one per
+           instance: the per-instance builds, which load each instance's entry, on a problem whose
+           every value is the shared one's;
+  costs    a cost table (cmpc_batch_set_instance_costs) of identical default rows alone;
+  both     both tables.
 
 Workloads: config 3 (N = 10, bench.py's instance mix), N = 16 trot and N = 20 (config 5's records,
 the solve alone). The shared form runs first and last (the drift of the run); forces must agree bit
 for bit between the forms.
 
-  python scripts/instance_params_probe.py [--batch 65536] [--reps 50]
+  python scripts/instance_params_probe.py [--batch 65536] [--reps 50] [--forms shared,table,shared_again]
+
+(--forms: a library from before the cost table, named by CMPC_LIB, runs the first two forms only)
 """
 import argparse
 import importlib
@@ -46,12 +51,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--forms", default="shared,table,costs,both,shared_again")
     args = ap.parse_args()
     cm = importlib.import_module("quad-periodic-mpc_amd")
     sm = importlib.import_module("quad-periodic-mpc_amd.solver")
     torch.cuda.set_stream(torch.cuda.Stream())
     B = args.batch
     table = torch.from_numpy(np.repeat(cm.make_instance_params(), B, axis=0)).cuda()
+    costs = torch.from_numpy(np.repeat(cm.make_instance_costs(), B, axis=0)).cuda()
+    forms = args.forms.split(",")
+    with_costs = "costs" in forms or "both" in forms
     out = {}
     for name, N, kw in (("config3", 10, {}), ("n16_trot", 16, dict(random_contact_frac=0.0)), ("n20", 20, {})):
         prm = cm.make_params(N)
@@ -61,15 +70,21 @@ def main():
         it = torch.empty(B, dtype=torch.int32, device="cuda")
         s = sm.BatchSolver(prm, max_batch=B, stream=torch.cuda.current_stream())
         res, digest = {}, {}
-        for form in ("shared", "table", "shared_again"):
-            s.set_instance_params(table if form == "table" else None)
+        for form in forms:
+            s.set_instance_params(table if form in ("table", "both") else None)
+            if with_costs:
+                s.set_instance_costs(costs if form in ("costs", "both") else None)
             res[form] = round(timed(s, recs, f, st, it, args.reps), 4)
             digest[form] = (f.cpu().numpy().tobytes(), st.cpu().numpy().tobytes())
             print(f"{name} B={B} {form}: {res[form]:.4f} ms/solve", flush=True)
         s.close()
-        res["ratio_table_to_shared"] = round(res["table"] / res["shared"], 4)
-        res["same_bits"] = digest["table"] == digest["shared"] == digest["shared_again"]
-        print(f"{name}: table / shared = {res['ratio_table_to_shared']:.4f}, same bits: {res['same_bits']}", flush=True)
+        tabled = [form for form in ("table", "costs", "both") if form in res]
+        for form in tabled:
+            res[f"ratio_{form}_to_shared"] = round(res[form] / res["shared"], 4)
+        res["same_bits"] = all(digest[form] == digest["shared"] for form in digest)
+        print(f"{name}: {' / '.join(tabled)} over shared = "
+              f"{' / '.join('%.4f' % res[f'ratio_{form}_to_shared'] for form in tabled)}, same bits: {res['same_bits']}",
+              flush=True)
         out[name] = res
     print(json.dumps(out))
 

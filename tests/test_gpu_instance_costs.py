@@ -1,0 +1,698 @@
+"""The per-instance cost table (cmpc_batch_set_instance_costs): state weights and alpha per instance.
+
+Instance i takes row i of a table of (12 weights, alpha), under the mix of tests/cost_mix.py (four
+cost combos, rotated over the batch so that every instance of every kernel family meets every combo),
+over param_sets.CASES, the smallest batches that reach every kernel family. The comparisons are of bits
+unless stated otherwise:
+
+  1. a table whose rows are all one combo is the shared handle of that combo (full and half due);
+  2. under the mixed table, row i is row i of the shared handle of its combo solving the whole batch
+     (every case, every rotation; with a due mask);
+  3. the mixed solve against the fp64 optimum of each row's own cost (cost_mix.cpu_data;
+     tests/test_instance_costs_ref.py is its CPU side), at the project's gates: 1e-4 at N <= 10,
+     1e-5 from N = 11, status 0, swing legs exactly zero;
+  4. both tables set: the 16 (model / mu / f_max, cost) pairs row by row and against the fp64 optimum;
+  5. one 16384-instance batch against four pieces of 4096 (the 60 / 64 split, the persistent builds);
+  6. the life cycle: clear, set_params, set_model, new shared values under one table, the two tables
+     in both orders, batch > count;
+  7. bad rows at a middle index, one test per kind; NaN in the reserved words;
+  8. a row of twelve zero weights: forces exactly +0.0;
+  9. evaluate, condense (both modes) and ADMM row by row against the shared handles; rollout and the
+     config-5 residual unchanged by a cost table;
+ 10. the failure contract under the mixed table;
+ 11. a closed loop of 64 robots, tick by tick against the shared-handle loops.
+"""
+import functools
+import importlib
+
+import numpy as np
+import pytest
+
+import cost_mix as cx
+import instance_mix as im
+import model_ref as mr
+import param_sets as ps
+from test_gpu_due import ST_FILL, IT_FILL, bits, sentinel_forces
+
+pytestmark = pytest.mark.gpu
+
+REF_TOL = 1e-4    # N <= 10: ours against the fp64 optimum
+FP64_TOL = 1e-5   # N >= 11 (refined)
+NC = cx.NC
+BAD_INPUT = 4     # CMPC_BAD_INPUT
+
+
+@pytest.fixture(scope="module")
+def solver_mod():
+    mod = importlib.import_module("quad-periodic-mpc_amd.solver")
+    mod.load_library()
+    return mod
+
+
+def _smod():
+    return importlib.import_module("quad-periodic-mpc_amd.solver")
+
+
+def _cm():
+    return importlib.import_module("quad-periodic-mpc_amd")
+
+
+def run(s, recs, due=None):
+    """One device solve into sentinel-filled buffers -> (forces, status, iters)."""
+    import torch
+    B, oc = recs.shape[0], s.out_cols
+    r = torch.from_numpy(np.array(recs, np.float32)).cuda()
+    f = torch.from_numpy(sentinel_forces(B, oc)).cuda()
+    st = torch.full((B,), ST_FILL, dtype=torch.uint8, device="cuda")
+    it = torch.full((B,), IT_FILL, dtype=torch.int32, device="cuda")
+    dd = None if due is None else torch.from_numpy(np.array(due, np.uint8)).cuda()
+    torch.cuda.synchronize()
+    s.solve(r, f, st, it, due=dd)
+    torch.cuda.synchronize()
+    return f.cpu().numpy(), st.cpu().numpy(), it.cpu().numpy()
+
+
+def assert_same_bits(got, want, msg=""):
+    for a, b in zip(got, want):
+        np.testing.assert_array_equal(bits(a), bits(b), err_msg=msg)
+
+
+def shared(k, N, B):
+    """A fresh shared handle of cost combo k (default robot, mu 0.4, f_max 120)."""
+    return _smod().BatchSolver(cx.combo_params(k, N), max_batch=B)
+
+
+def cost_handle(N, B, tab):
+    """A default handle (default weights, alpha 4e-5) with the cost table set."""
+    s = _smod().BatchSolver(_cm().make_params(N), max_batch=B)
+    try:
+        s.set_instance_costs(tab)
+    except Exception:
+        s.close()
+        raise
+    return s
+
+
+def half_due(B, seed=5):
+    due = np.zeros(B, np.uint8)
+    due[np.random.default_rng(seed).choice(B, B // 2, replace=False)] = 1
+    return due
+
+
+def nan_where_not_due(recs, due):
+    out = np.array(recs, np.float32)
+    out[due == 0] = np.nan
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def shared_solve(k, case):
+    """(forces, status, iters) of the case's whole batch on the shared handle of cost combo k; once per process."""
+    N = ps.CASES[case][0]
+    recs = ps.case_records("default", case)
+    with mr.closing(shared(k, N, len(recs))) as s:
+        out = run(s, recs)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def rowwise(case, ids):
+    """Row i of the shared handle of cost combo ids[i]."""
+    outs = [shared_solve(k, case) for k in range(NC)]
+    return tuple(np.stack([outs[k][j][i] for i, k in enumerate(ids)]) for j in range(3))
+
+
+def _rows_of(outs, ids):
+    """outs[k]: an array (or tuple of arrays) of combo k's shared handle -> row i from combo ids[i]."""
+    if isinstance(outs[0], tuple):
+        return tuple(_rows_of([o[j] for o in outs], ids) for j in range(len(outs[0])))
+    return np.stack([outs[k][i] for i, k in enumerate(ids)])
+
+
+# ---- 1: a uniform table is the shared handle ---------------------------------------------------------
+@pytest.mark.parametrize("masked", [False, True], ids=["full", "due"])
+@pytest.mark.parametrize("k", [1, 3])
+@pytest.mark.parametrize("case", ["n10_families", "n16_trot", "n20_standing"])
+def test_uniform_table_is_the_shared_handle(cm, solver_mod, case, k, masked):
+    N = ps.CASES[case][0]
+    recs = ps.case_records("default", case)
+    B = len(recs)
+    due = half_due(B) if masked else None
+    rin = nan_where_not_due(recs, due) if masked else recs
+    with mr.closing(shared(k, N, B)) as s:
+        want = run(s, rin, due)
+        assert s.instance_cost_count() == 0
+    m = np.ones(B, bool) if due is None else due != 0
+    assert (want[1][m] == 0).mean() > 0.9 and (want[1][~m] == ST_FILL).all()
+    np.testing.assert_array_equal(bits(want[0][~m]), bits(sentinel_forces(B, 12 * N)[~m]))
+    with mr.closing(cost_handle(N, B, cx.combo_rows(np.full(B, k)))) as s:
+        assert s.instance_cost_count() == B and s.instance_count == 0
+        assert_same_bits(run(s, rin, due), want, f"uniform table of cost combo {k}")
+    with mr.closing(solver_mod.BatchSolver(cm.make_params(N), max_batch=B)) as s:
+        assert not np.array_equal(bits(run(s, rin, due)[0])[m], bits(want[0])[m])   # combo k is not the default
+
+
+# ---- 2: the mixed table, row by row -----------------------------------------------------------------
+@pytest.mark.parametrize("s_rot", range(NC))
+@pytest.mark.parametrize("case", list(ps.CASES))
+def test_mixed_table_row_by_row(cm, solver_mod, case, s_rot):
+    N = ps.CASES[case][0]
+    recs = ps.case_records("default", case)
+    B = len(recs)
+    ids = cx.combo_ids(B, s_rot)
+    if case == "n10_families":
+        counts = ps.family_counts(recs)
+        assert min(counts) > 0, counts   # c1-60, c1-64, tail, w80, w96, w120
+    want = rowwise(case, ids)
+    with mr.closing(cost_handle(N, B, cx.table(B, s_rot))) as s:
+        got = run(s, recs)
+    assert_same_bits(got, want, f"{case} rotation {s_rot}")
+    assert (got[1] == 0).mean() > 0.9
+    dflt = shared_solve(0, case)
+    differ = (bits(got[0]) != bits(dflt[0])).any(1)
+    assert differ[(ids != 0) & (got[1] == 0) & (np.abs(dflt[0]).max(1) > 0)].all()
+
+
+@pytest.mark.parametrize("s_rot", [0, 3])
+@pytest.mark.parametrize("case", ["n10_families", "n16_trot"])
+def test_mixed_table_under_a_due_mask(cm, solver_mod, case, s_rot):
+    N = ps.CASES[case][0]
+    recs = ps.case_records("default", case)
+    B = len(recs)
+    ids = cx.combo_ids(B, s_rot)
+    due = half_due(B, seed=7 + s_rot)
+    m = due != 0
+    want = rowwise(case, ids)
+    with mr.closing(cost_handle(N, B, cx.table(B, s_rot))) as s:
+        got = run(s, nan_where_not_due(recs, due), due)
+    for g, w in zip(got, want):
+        np.testing.assert_array_equal(bits(g[m]), bits(w[m]))   # row i is row i of the table, mask or not
+    np.testing.assert_array_equal(bits(got[0][~m]), bits(sentinel_forces(B, 12 * N)[~m]))
+    assert (got[1][~m] == ST_FILL).all() and (got[2][~m] == IT_FILL).all()
+
+
+# ---- 3: against the fp64 optimum of each row's own cost ----------------------------------------------
+@pytest.mark.parametrize("case", list(ps.CASES))
+def test_mixed_table_against_the_fp64_optimum(cm, orc, solver_mod, case):
+    """Measured on an MI355X when this test was written: see DESIGN.md §3.4."""
+    if not orc.ref_available():
+        pytest.skip("oracle/_ref not present")
+    d = cx.cpu_data(case, 0)
+    N, recs, ids, x64 = d["N"], d["recs"], d["ids"], d["x64"]
+    assert (d["ri64"] == 0).all(), d["ri64"]
+    with mr.closing(cost_handle(N, len(recs), cx.table(len(recs), 0))) as s:
+        f, st, it = run(s, recs)
+    e64 = ps.rel_dist(f, x64)
+    per = [float(e64[ids == k].max()) for k in range(NC)]
+    print(f"[cost] {case}: {len(recs)} instances under the mix, ours within {e64.max():.1e} of the fp64 optimum "
+          f"(per combo {', '.join(f'{v:.1e}' for v in per)}; mean iters {it.mean():.1f})")
+    swing = np.repeat(cm.unpack_gait(recs, N) == 0, 3, axis=1)
+    assert np.all(f[swing] == 0.0)
+    assert (st == 0).all(), np.bincount(st)
+    gate = REF_TOL if N <= 10 else FP64_TOL
+    assert e64.max() <= gate, (float(e64.max()), int(e64.argmax()), int(ids[e64.argmax()]))
+
+
+# ---- 4: both tables ----------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def pair_solve(km, kc, case):
+    """The case's whole batch on the shared handle of the pair (instance_mix combo km, cost combo kc)."""
+    N = ps.CASES[case][0]
+    recs = ps.case_records("default", case)
+    with mr.closing(_smod().BatchSolver(cx.pair_params(km, kc, N), max_batch=len(recs),
+                                        model=im.combo_model(km))) as s:
+        out = run(s, recs)
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+@pytest.mark.parametrize("order", ["params_first", "costs_first"])
+@pytest.mark.parametrize("case", ["n10_families", "n3_padding", "n16_trot"])
+def test_both_tables_row_by_row(cm, solver_mod, case, order):
+    N = ps.CASES[case][0]
+    recs = ps.case_records("default", case)
+    B = len(recs)
+    mids, cids = cx.pair_ids(B)
+    want = tuple(np.stack([pair_solve(int(km), int(kc), case)[j][i] for i, (km, kc) in enumerate(zip(mids, cids))])
+                 for j in range(3))
+    with mr.closing(solver_mod.BatchSolver(cm.make_params(N), max_batch=B)) as s:
+        if order == "params_first":
+            s.set_instance_params(im.combo_rows(mids))
+            s.set_instance_costs(cx.combo_rows(cids))
+        else:
+            s.set_instance_costs(cx.combo_rows(cids))
+            s.set_instance_params(im.combo_rows(mids))
+        assert s.instance_count == B and s.instance_cost_count() == B
+        got = run(s, recs)
+    assert_same_bits(got, want, f"{case}, both tables ({order})")
+    assert (got[1] == 0).mean() > 0.9
+
+
+@pytest.mark.parametrize("case", ["n10_families", "n3_padding", "n16_trot"])
+def test_both_tables_against_the_fp64_optimum(cm, orc, solver_mod, case):
+    """Measured on an MI355X when this test was written: see DESIGN.md §3.4."""
+    if not orc.ref_available():
+        pytest.skip("oracle/_ref not present")
+    d = cx.cpu_data_pairs(case)
+    N, recs, x64 = d["N"], d["recs"], d["x64"]
+    B = len(recs)
+    assert (d["ri64"] == 0).all(), d["ri64"]
+    with mr.closing(solver_mod.BatchSolver(cm.make_params(N), max_batch=B)) as s:
+        s.set_instance_params(im.combo_rows(d["mids"]))
+        s.set_instance_costs(cx.combo_rows(d["cids"]))
+        f, st, it = run(s, recs)
+    e64 = ps.rel_dist(f, x64)
+    print(f"[cost] {case}, both tables: ours within {e64.max():.1e} of the fp64 optimum "
+          f"(instance {int(e64.argmax())}: model combo {int(d['mids'][e64.argmax()])}, cost combo "
+          f"{int(d['cids'][e64.argmax()])})")
+    swing = np.repeat(cm.unpack_gait(recs, N) == 0, 3, axis=1)
+    assert np.all(f[swing] == 0.0)
+    assert (st == 0).all(), np.bincount(st)
+    assert e64.max() <= (REF_TOL if N <= 10 else FP64_TOL), float(e64.max())
+
+
+# ---- 5: launch forms ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("N", [10, 16])
+def test_launch_forms_agree_under_the_mix(cm, solver_mod, N):
+    """One 16384-instance random-contact batch (at N = 10 the 60 / 64 split of class 1, the persistent
+    sparse wide classes, the grid hint) against the same records and rows in four pieces of 4096."""
+    B, P = 16384, 4096
+    prm = cm.make_params(N)
+    recs = cm.make_instances(B, N, seed=8500 + N, random_contact_frac=1.0)
+    tab = cx.table(B, 1)
+    with mr.closing(solver_mod.BatchSolver(prm, max_batch=B)) as s:
+        s.set_instance_costs(tab)
+        f_all, st_all, it_all = s.solve_host(recs)
+    parts = []
+    with mr.closing(solver_mod.BatchSolver(prm, max_batch=P)) as s:
+        for a in range(0, B, P):
+            s.set_instance_costs(tab[a:a + P])
+            parts.append(s.solve_host(recs[a:a + P]))
+    f_p, st_p, it_p = (np.concatenate([p[j] for p in parts]) for j in range(3))
+    diff = np.nonzero((bits(f_p) != bits(f_all)).any(1) | (st_p != st_all) | (it_p != it_all))[0]
+    assert diff.size == 0, (diff.size, diff[:8])
+    assert (st_all == 0).mean() > 0.99
+    with mr.closing(solver_mod.BatchSolver(prm, max_batch=P)) as s:
+        f_def = s.solve_host(recs[:P])[0]
+    ids = cx.combo_ids(P, 1)
+    same = (bits(f_def) == bits(f_all[:P])).all(1)
+    assert same[ids == 0].all()                       # combo 0 is the default handle
+    assert not same[(ids != 0) & (np.abs(f_def).max(1) > 0)].any()
+
+
+# ---- 6: life cycle -----------------------------------------------------------------------------------
+def test_clear_and_survive(cm, solver_mod):
+    recs10 = ps.case_records("default", "n10_families")
+    recs16 = ps.case_records("default", "n16_trot")
+    B = len(recs10)
+    p10, p16 = cm.make_params(10), cm.make_params(16)
+    tab = cx.table(B, 2)
+    want10 = rowwise("n10_families", cx.combo_ids(B, 2))
+    want16 = rowwise("n16_trot", cx.combo_ids(len(recs16), 2))
+    with mr.closing(solver_mod.BatchSolver(p10, max_batch=B)) as s:
+        fresh = run(s, recs10)
+        s.set_instance_costs(tab)
+        assert s.instance_cost_count() == B
+        assert_same_bits(run(s, recs10), want10, "table set")
+        s.set_params(p16)                                  # the table survives set_params
+        assert s.instance_cost_count() == B
+        assert_same_bits(run(s, recs16), want16, "N = 16 under the same table")
+        s.set_params(cx.combo_params(3, 10))               # shared weights and alpha stay hidden
+        assert_same_bits(run(s, recs10), want10, "back at N = 10")
+        s.set_params(p10)
+        s.set_instance_costs(None)                         # clear: a fresh handle's bits
+        assert s.instance_cost_count() == 0
+        assert_same_bits(run(s, recs10), fresh, "cleared")
+        s.set_params(cx.combo_params(1, 10))
+        s.set_instance_costs(tab)
+        s.set_instance_costs(None)                         # what was set under the table shows again
+        assert_same_bits(run(s, recs10), shared_solve(1, "n10_families"), "shared values after a clear")
+
+
+def test_new_shared_values_reach_every_row_of_a_cost_table(cm, solver_mod):
+    """With only the cost table set, a later set_model and a changed mu / f_max apply to every row."""
+    case = "n10_families"
+    recs = ps.case_records("default", case)
+    B = len(recs)
+    cids = cx.combo_ids(B, 1)
+    km = 1                                                 # instance_mix "heavy", mu 0.6, f_max 150
+    want = tuple(np.stack([pair_solve(km, int(kc), case)[j][i] for i, kc in enumerate(cids)]) for j in range(3))
+    with mr.closing(cost_handle(10, B, cx.table(B, 1))) as s:
+        before = run(s, recs)
+        assert_same_bits(before, rowwise(case, cids), "default robot under the cost table")
+        s.set_model(im.combo_model(km))
+        s.set_params(im.combo_params(km, 10))              # (its weights and alpha, the defaults, stay hidden)
+        assert s.instance_cost_count() == B and s.instance_count == 0
+        got = run(s, recs)
+        assert_same_bits(got, want, "new model, mu and f_max under the cost table")
+        assert not np.array_equal(bits(got[0]), bits(before[0]))
+        s.set_model(None)
+        s.set_params(cm.make_params(10))
+        assert_same_bits(run(s, recs), before, "and back")
+
+
+def test_new_shared_weights_reach_every_row_of_a_parameter_table(cm, solver_mod):
+    """With only the parameter table set, changed shared weights and alpha apply to every row."""
+    case = "n10_families"
+    recs = ps.case_records("default", case)
+    B = len(recs)
+    mids = im.combo_ids(B, 0)
+    kc = 3
+    want = tuple(np.stack([pair_solve(int(km), kc, case)[j][i] for i, km in enumerate(mids)]) for j in range(3))
+    with mr.closing(solver_mod.BatchSolver(cm.make_params(10), max_batch=B, instance_params=im.table(B, 0))) as s:
+        before = run(s, recs)
+        s.set_params(cx.combo_params(kc, 10))
+        assert s.instance_count == B and s.instance_cost_count() == 0
+        got = run(s, recs)
+        assert_same_bits(got, want, "new shared weights and alpha under the parameter table")
+        assert not np.array_equal(bits(got[0]), bits(before[0]))
+        s.set_params(cm.make_params(10))
+        assert_same_bits(run(s, recs), before, "and back")
+
+
+def test_tables_are_cleared_independently(cm, solver_mod):
+    case = "n10_families"
+    recs = ps.case_records("default", case)
+    B = len(recs)
+    mids, cids = cx.pair_ids(B)
+    both = tuple(np.stack([pair_solve(int(km), int(kc), case)[j][i] for i, (km, kc) in enumerate(zip(mids, cids))])
+                 for j in range(3))
+    only_cost = rowwise(case, cids)
+    only_par = tuple(np.stack([pair_solve(int(km), 0, case)[j][i] for i, km in enumerate(mids)]) for j in range(3))
+    with mr.closing(solver_mod.BatchSolver(cm.make_params(10), max_batch=B)) as s:
+        fresh = run(s, recs)
+        s.set_instance_costs(cx.combo_rows(cids))
+        s.set_instance_params(im.combo_rows(mids))
+        assert_same_bits(run(s, recs), both, "both")
+        s.set_instance_params(None)                        # the cost table stays
+        assert (s.instance_count, s.instance_cost_count()) == (0, B)
+        assert_same_bits(run(s, recs), only_cost, "parameter table cleared")
+        s.set_instance_params(im.combo_rows(mids))
+        s.set_instance_costs(None)                         # the parameter table stays
+        assert (s.instance_count, s.instance_cost_count()) == (B, 0)
+        assert_same_bits(run(s, recs), only_par, "cost table cleared")
+        s.set_instance_costs(cx.combo_rows(cids))
+        assert_same_bits(run(s, recs), both, "both again")
+        s.set_instance_costs(None)
+        s.set_instance_params(None)
+        assert_same_bits(run(s, recs), fresh, "neither")
+
+
+def test_batch_beyond_either_table_is_refused(cm, solver_mod):
+    import torch
+    recs = ps.case_records("default", "n3_padding")
+    B = len(recs)
+    with mr.closing(solver_mod.BatchSolver(cm.make_params(3), max_batch=B)) as s:
+        r = torch.from_numpy(np.array(recs)).cuda()
+        f = torch.from_numpy(sentinel_forces(B, 36)).cuda()
+        st = torch.full((B,), ST_FILL, dtype=torch.uint8, device="cuda")
+        it = torch.full((B,), IT_FILL, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+
+        def refused():
+            with pytest.raises(solver_mod.CmpcError, match=r"\(-1\)"):
+                s.solve(r, f, st, it)
+            with pytest.raises(solver_mod.CmpcError, match=r"\(-1\)"):
+                s.solve(r, f, st, it, due=torch.ones(B, dtype=torch.uint8, device="cuda"))
+            with pytest.raises(solver_mod.CmpcError):
+                s.solve_host(recs)
+            with pytest.raises(solver_mod.CmpcError):
+                s.evaluate_host(recs, np.zeros((B, 36), np.float32))
+            torch.cuda.synchronize()
+            np.testing.assert_array_equal(bits(f.cpu().numpy()), bits(sentinel_forces(B, 36)))
+            assert (st.cpu().numpy() == ST_FILL).all() and (it.cpu().numpy() == IT_FILL).all()
+
+        s.set_instance_costs(cx.table(B - 8, 0))           # the cost table alone, short
+        assert s.instance_cost_count() == B - 8
+        refused()
+        assert (s.solve_host(recs[:B - 8])[1] == 0).mean() > 0.9   # within the table: solved
+        s.set_instance_params(im.table(B, 0))              # a full parameter table beside it: still short
+        refused()
+        s.set_instance_costs(cx.table(B, 0))
+        s.set_instance_params(im.table(B - 4, 0))          # now the parameter table is the short one
+        refused()
+        assert (s.solve_host(recs[:B - 4])[1] == 0).mean() > 0.9
+        with pytest.raises(solver_mod.CmpcError, match=r"\(-1\)"):
+            s.set_instance_costs(cx.table(B + 1, 0))       # count > max_batch
+        assert s.instance_cost_count() == B
+
+
+# ---- 7: bad rows -------------------------------------------------------------------------------------
+BAD = {
+    "nan_weight": (3, float("nan")),
+    "inf_weight": (5, float("inf")),
+    "neg_inf_weight": (0, float("-inf")),
+    "negative_weight": (8, -0.3),
+    "alpha_zero": (12, 0.0),
+    "alpha_negative": (12, -4e-5),
+    "alpha_nan": (12, float("nan")),
+    "alpha_2e38": (12, 2e38),     # finite, but 2.f * alpha overflows
+}
+
+
+@pytest.mark.parametrize("kind", list(BAD))
+def test_a_bad_row_is_rejected(cm, solver_mod, kind):
+    """A bad row at a middle index: -2, and the previous table (or none) stays in force."""
+    recs = ps.case_records("default", "n3_padding")
+    B = len(recs)
+    word, val = BAD[kind]
+    with mr.closing(solver_mod.BatchSolver(cm.make_params(3), max_batch=B)) as s:
+        fresh = run(s, recs)
+        t = cx.table(B, 1)
+        t[B // 2, word] = val
+        with pytest.raises(solver_mod.CmpcError, match=r"\(-2\)"):   # no table yet: none afterwards
+            s.set_instance_costs(t)
+        assert s.instance_cost_count() == 0
+        assert_same_bits(run(s, recs), fresh, "a rejected first table")
+        s.set_instance_costs(cx.table(B, 1))
+        want = run(s, recs)
+        assert not np.array_equal(bits(want[0]), bits(fresh[0]))
+        t = cx.table(B, 2)
+        t[B // 2, word] = val
+        with pytest.raises(solver_mod.CmpcError, match=r"\(-2\)"):
+            s.set_instance_costs(t)
+        assert s.instance_cost_count() == B
+        assert_same_bits(run(s, recs), want, "after a rejected table")
+
+
+def test_reserved_words_are_not_read(cm, solver_mod):
+    recs = ps.case_records("default", "n3_padding")
+    B = len(recs)
+    t = cx.table(B, 1)
+    with mr.closing(cost_handle(3, B, t)) as s:
+        want = run(s, recs)
+        t2 = t.copy()
+        t2[:, 13:] = np.nan
+        t2[B // 2, 13:] = np.float32([np.inf, -1.0, -np.inf])
+        s.set_instance_costs(t2)
+        assert s.instance_cost_count() == B
+        assert_same_bits(run(s, recs), want, "NaN in the reserved words")
+
+
+# ---- 8: a degenerate cost ----------------------------------------------------------------------------
+# one row per kernel family of n10_families (reduced sizes 48, 63, 66, 75, 81, 99: class 1's 60- and
+# 64-wide builds, the tail class, wide 80 / 96 / 120), and the refining wide builds at N = 16 (96
+# columns) and N = 20 (256 columns)
+ZERO_HIT = {"n10_families": [127, 64, 3, 42, 54, 41], "n16_trot": [5], "n20_standing": [1]}
+
+
+@pytest.mark.parametrize("case", list(ZERO_HIT))
+def test_zero_weights_give_zero_forces(cm, solver_mod, case):
+    """Twelve zero weights, alpha 4e-5: H = 2 alpha I, g = 0, so the forces are exactly +0.0 with status
+    0; every other row keeps its bits. (The tail and wide classes form the unconstrained minimiser as
+    x = -(J y), which is -0.0 under a zero gradient; their per-instance builds take 0 - (J y).)"""
+    N = ps.CASES[case][0]
+    recs = ps.case_records("default", case)
+    B = len(recs)
+    hit = ZERO_HIT[case]
+    if case == "n10_families":
+        n = ps.reduced_sizes(recs, N)[hit]
+        assert [int(np.searchsorted(ps.FAMILY_EDGES, v, side="left")) for v in n] == [1, 2, 3, 4, 5, 6], n
+    want = rowwise(case, cx.combo_ids(B, 0))
+    tab = cx.table(B, 0)
+    tab[hit, :12] = 0.0
+    tab[hit, 12] = 4e-5
+    with mr.closing(cost_handle(N, B, tab)) as s:
+        f, st, it = run(s, recs)
+    keep = np.ones(B, bool)
+    keep[hit] = False
+    neg = {i: int((bits(f[i]) == 0x80000000).sum()) for i in hit}
+    print(f"[cost] {case}, zero weights: words equal to -0.0 per instance {neg}, status {st[hit]}")
+    assert (bits(f[hit]) == 0).all() and (st[hit] == 0).all(), neg
+    for g, w in zip((f, st, it), want):
+        np.testing.assert_array_equal(bits(g[keep]), bits(w[keep]))
+
+
+# ---- 9: the other entry points, row by row against the shared handles --------------------------------
+@pytest.mark.parametrize("case,k", [("n10_families", 32), ("n20_standing", 4)])
+def test_evaluate_row_by_row(cm, solver_mod, case, k):
+    N = ps.CASES[case][0]
+    recs = ps.case_records("default", case)[:k]
+    ids = cx.combo_ids(k, 1)
+    f = rowwise(case, cx.combo_ids(len(ps.case_records("default", case)), 1))[0][:k]
+    outs = []
+    for c in range(NC):
+        with mr.closing(shared(c, N, k)) as s:
+            outs.append(s.evaluate_host(recs, f))
+    want = _rows_of(outs, ids)
+    with mr.closing(cost_handle(N, k, cx.table(k, 1))) as s:
+        got = s.evaluate_host(recs, f)
+    np.testing.assert_array_equal(bits(got[0]), bits(want[0]))                       # x_pred
+    np.testing.assert_array_equal(got[1].view(np.uint64), want[1].view(np.uint64))   # all eight words
+    assert not np.array_equal(got[1][ids != 0], outs[0][1][ids != 0])
+
+
+def _condense_hook(s, recs, B, N, rows):
+    import torch
+    H = torch.zeros((B, 12 * N, 12 * N), dtype=torch.float32, device="cuda")
+    g = torch.zeros((B, 12 * N), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    s.condense(recs, H, g, rows=rows)
+    torch.cuda.synchronize()
+    return H.cpu().numpy(), g.cpu().numpy()
+
+
+@pytest.mark.parametrize("rows", [False, True], ids=["mirrored", "rows"])
+@pytest.mark.parametrize("N", [3, 10])
+def test_condense_row_by_row(cm, solver_mod, N, rows):
+    import torch
+    B = 8
+    recs = torch.from_numpy(cm.make_instances(B, N, seed=9600 + N, random_contact_frac=1.0)).cuda()
+    ids = cx.combo_ids(B, 3)
+    outs = []
+    for c in range(NC):
+        with mr.closing(shared(c, N, B)) as s:
+            outs.append(_condense_hook(s, recs, B, N, rows))
+    want = _rows_of(outs, ids)
+    with mr.closing(cost_handle(N, B, cx.table(B, 3))) as s:
+        got = _condense_hook(s, recs, B, N, rows)
+    assert_same_bits(got, want, "condense")
+    assert not np.array_equal(got[0][ids != 0], outs[0][0][ids != 0])
+
+
+def test_admm_row_by_row(cm, solver_mod):
+    import torch
+    from test_gpu_admm import TIGHT
+    N, B = 3, 16
+    recs = torch.from_numpy(np.ascontiguousarray(cm.make_instances(B, N, seed=9699))).cuda()
+    ids = cx.combo_ids(B, 0)
+
+    def admm(s):
+        H = torch.empty((B, 12 * N, 12 * N), dtype=torch.float32, device="cuda")
+        gv = torch.empty((B, 12 * N), dtype=torch.float32, device="cuda")
+        f = torch.empty((B, 12 * N), dtype=torch.float32, device="cuda")
+        status = torch.empty(B, dtype=torch.uint8, device="cuda")
+        iters = torch.empty(B, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        s.condense(recs, H, gv)
+        s.admm(recs, H, gv, f, status, iters, settings=solver_mod.admm_settings(**TIGHT))
+        torch.cuda.synchronize()
+        return f.cpu().numpy(), status.cpu().numpy(), iters.cpu().numpy()
+
+    outs = []
+    for c in range(NC):
+        with mr.closing(shared(c, N, B)) as s:
+            outs.append(admm(s))
+    want = _rows_of(outs, ids)
+    with mr.closing(cost_handle(N, B, cx.table(B, 0))) as s:
+        got = admm(s)
+    assert_same_bits(got, want, "admm")
+    assert (bits(got[0][ids != 0]) != bits(outs[0][0][ids != 0])).any(1).all()
+
+
+def test_rollout_and_residual_do_not_read_the_cost(cm, solver_mod):
+    import torch
+    inst = importlib.import_module("quad-periodic-mpc_amd.instances")
+    N, B = 10, 64
+    recs = cm.make_instances(B, N, seed=9677)
+    g = np.random.Generator(np.random.Philox(13))
+    u = np.zeros((B, 12 * N), np.float32)
+    u[:, :12] = g.normal(0, 20, (B, 12))
+    xi = g.normal(0, 2, (B, 6)).astype(np.float32)
+    due = half_due(B, seed=4)
+    loco = inst.make_loco_states(B, seed=11)
+    logs = cm.make_logs(recs, seed=9689)
+    d_rec, d_u, d_xi, d_due = (torch.from_numpy(a).cuda() for a in (recs, u, xi, due))
+
+    def both(s):
+        d_loco = torch.from_numpy(loco.copy()).cuda()
+        d_r = torch.from_numpy(np.array(recs, np.float32)).cuda()
+        d_log = torch.from_numpy(np.ascontiguousarray(logs)).cuda()
+        est = torch.zeros((B, 816), dtype=torch.float32, device="cuda")
+        fext6 = torch.full((B, 6), np.nan, dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        s.rollout(d_loco, d_rec, d_u, xi6=d_xi, due=d_due)
+        s.estimate(est, d_r, logs=d_log, sim_time=1.0, fext6=fext6)
+        torch.cuda.synchronize()
+        return d_loco.cpu().numpy(), fext6.cpu().numpy(), est.cpu().numpy()
+
+    with mr.closing(solver_mod.BatchSolver(cm.make_params(N), max_batch=B)) as s:
+        want = both(s)
+        s.set_instance_costs(cx.table(B, 1))
+        got = both(s)
+    assert_same_bits(got, want, "rollout / residual under a cost table")
+    assert (bits(want[0][due != 0]) != bits(loco[due != 0])).any()
+
+
+# ---- 10: the failure contract ------------------------------------------------------------------------
+def test_a_nan_velocity_refuses_that_instance_alone(cm, solver_mod):
+    case = "n10_families"
+    recs = np.array(ps.case_records("default", case), np.float32)
+    B = len(recs)
+    ids = cx.combo_ids(B, 2)
+    want = rowwise(case, ids)
+    hit = B // 2 + 1
+    recs[hit, importlib.import_module("quad-periodic-mpc_amd.records").REC_V + 1] = np.nan
+    with mr.closing(cost_handle(10, B, cx.table(B, 2))) as s:
+        f, st, it = run(s, recs)
+    assert st[hit] == BAD_INPUT and (bits(f[hit]) == 0).all()
+    keep = np.arange(B) != hit
+    for g, w in zip((f, st, it), want):
+        np.testing.assert_array_equal(bits(g[keep]), bits(w[keep]))
+
+
+# ---- 11: closed loop ---------------------------------------------------------------------------------
+def test_closed_loop_tick_by_tick(cm, solver_mod):
+    """64 robots, 16 per combo: assemble -> solve -> rollout for 10 MPC steps under the cost table; every
+    robot's state and forces equal, tick by tick, the same robot in a shared-handle loop of its combo."""
+    import torch
+    inst = importlib.import_module("quad-periodic-mpc_amd.instances")
+    R = importlib.import_module("quad-periodic-mpc_amd.records")
+    N, B, STEPS, ITERS = 10, 64, 10, 13
+    ids = cx.combo_ids(B, 0)
+    loco0 = inst.make_loco_states(B, seed=21, gaits=("trotting",), omni_frac=1.0, first_run_frac=1.0)
+    ints = loco0.view(np.int32)
+    ints[:, R.LOCO_COUNTER] = ITERS * (ints[:, R.LOCO_COUNTER] // ITERS)   # every robot due on the same tick
+    lp = R.make_loco_params(0.002, ITERS, 0.0)
+
+    def loop(s):
+        d_loco = torch.from_numpy(loco0.copy()).cuda()
+        d_rec = torch.zeros((B, R.record_words(N)), dtype=torch.float32, device="cuda")
+        d_due = torch.zeros(B, dtype=torch.uint8, device="cuda")
+        f = torch.zeros((B, 12 * N), dtype=torch.float32, device="cuda")
+        st = torch.zeros(B, dtype=torch.uint8, device="cuda")
+        trace = []
+        for _ in range(STEPS):
+            for _ in range(ITERS):                 # ITERS control ticks, the last one is due
+                s.assemble(d_loco, lp, d_rec, d_due)
+            s.solve(d_rec, f, st)
+            s.rollout(d_loco, d_rec, f, due=d_due)
+            torch.cuda.synchronize()
+            trace.append((d_loco.cpu().numpy(), f.cpu().numpy(), st.cpu().numpy(), d_due.cpu().numpy()))
+        return trace
+
+    outs = []
+    for c in range(NC):
+        with mr.closing(shared(c, N, B)) as s:
+            outs.append(loop(s))
+    with mr.closing(cost_handle(N, B, cx.table(B, 0))) as s:
+        got = loop(s)
+    for t in range(STEPS):
+        want = _rows_of([tuple(o[t]) for o in outs], ids)
+        assert_same_bits(got[t], want, f"tick {t}")
+        assert got[t][3].all() and (got[t][2] == 0).mean() > 0.9
+    last = STEPS - 1
+    m = ids != 0
+    assert (bits(got[last][0][m]) != bits(outs[0][last][0][m])).any(1).all()   # the cost reaches the state
