@@ -22,7 +22,7 @@ SOURCES = ["cmpc_tail.hip", "cmpc_wide_w256.hip", "cmpc_wide_w192.hip", "cmpc_cl
            "cmpc_wide_w120.hip", "cmpc_wide_w128.hip", "cmpc_wide_w144.hip", "cmpc_wide_w80p.hip",
            "cmpc_wide_w96p.hip", "cmpc_wide_w120p.hip", "cmpc_wide_w128p.hip", "cmpc_wide_w80r.hip",
            "cmpc_wide_w96r.hip", "cmpc_wide_w120r.hip", "cmpc_wide_w80pr.hip", "cmpc_wide_w96pr.hip",
-           "cmpc_wide_w120pr.hip", "cmpc_wide_w96prd.hip", "cmpc_wide_w120prd.hip", "cmpc_wide_w96rd.hip", "cmpc_wide_w120rd.hip", "cmpc_condense.hip", "cmpc_launch.hip", "cmpc_estimator.hip", "cmpc_assemble.hip",
+           "cmpc_wide_w120pr.hip", "cmpc_wide_w96prd.hip", "cmpc_wide_w120prd.hip", "cmpc_wide_w96rd.hip", "cmpc_wide_w120rd.hip", "cmpc_condense.hip", "cmpc_launch.hip", "cmpc_inst_table.hip", "cmpc_estimator.hip", "cmpc_assemble.hip",
            "cmpc_admm.hip", "cmpc_quadprog.hip", "cmpc_evaluate.hip", "cmpc_condense_inst.hip",
            "cmpc_evaluate_inst.hip", "cmpc_abi.cpp"]
 ARCH = os.environ.get("CMPC_OFFLOAD_ARCH", "gfx950")
@@ -139,6 +139,18 @@ def build_tools(lib: str = LIB) -> str:
                         f"-Wl,-rpath,$ORIGIN", f"-Wl,-rpath,{PKG}"], check=True)
         os.replace(exe + ".tmp", exe)
     build_mfma_probe()
+    build_plan_dump()
+    return exe
+
+
+def build_plan_dump() -> str:
+    """cmpc_plan_dump: prints the launch plan of a batched solve (csrc/cmpc_plan.h). Compiled by the
+    host compiler alone, which keeps that header free of HIP; tests/test_launch_plan.py runs it."""
+    exe = os.path.join(PKG, "cmpc_plan_dump")
+    src = os.path.join(CSRC, "tools", "cmpc_plan_dump.cpp")
+    if _stale(exe, [src, os.path.join(CSRC, "cmpc_plan.h")]):
+        subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-o", exe + ".tmp", src], check=True)
+        os.replace(exe + ".tmp", exe)
     return exe
 
 

@@ -6,10 +6,12 @@
 #include <stdlib.h>
 
 #include "../../include/cmpc_solver.h"
+#include "cmpc_plan.h"
 
 namespace cmpc {
 
-// Launch-placement knobs of the A/B experiments: read from the environment only
+// Launch-placement knobs of the A/B experiments (PlanKnobs, cmpc_plan.h, holds the
+// ones of launch_solve): read from the environment only
 // in a diagnostic build (-DCMPC_DIAG_KNOBS=1, scripts/build_diag_variant.sh); the product build
 // always runs the measured defaults.
 inline int diag_knob(const char* name, int dflt) {
@@ -92,25 +94,11 @@ struct LocoParams {
 };
 
 // Scratch ints needed by launch_solve for max_batch instances.
-// d_work: [0] instances above class 1's build, [1 + list] lengths of the class lists, then the
-// lists of max_batch entries each. Instance lists of the classify pass: 80, 96, 128, 192, 256,
-// 5: class 1's own instances from N = 11 (n <= its row width; up to N = 10 it runs over the whole
-// batch), 144, and 7: class-1 instances with 60 < n <= 64 (the 64-wide class-1 build beside the
-// 60-wide one); 8: the 120-column wide build (97 <= n <= 120; the 128 build keeps 121..128).
-// 9: the tail class (cmpc_tail.hip, N <= 10: 64 < n <= 72, one wavefront each); 10: the instances
-// it hands to the 80-column wide class (an active set past 64 positions).
-// d_work = [2 headers of kHdr ints: cnt[0] total, cnt[1 + list] list lengths, cnt[kDeq + list] the
-// persistent wide workgroups' dequeue counters] [kLists lists of max_batch]. The solves alternate
+// d_work = [2 headers of kHdr ints: cnt[0] instances above class 1's build, cnt[1 + list] list
+// lengths, cnt[kDeq + list] the persistent wide workgroups' dequeue counters (the constants and the
+// size class of every list: cmpc_plan.h)] [kLists lists of max_batch]. The solves alternate
 // over the two headers: each classify pass zeroes the header the next solve uses (the previous
 // solve, which used it, has joined by then), so no memset precedes a solve (zeroed at create)
-constexpr int kLists = 11;
-constexpr int kHdr = 32;
-constexpr int kDeq = 16;  // cnt[kDeq + list]: dequeue counter of a persistent class's workgroups
-constexpr int kHdrBatch = 31;  // cnt[kHdrBatch]: the batch of the solve that counted into the header
-                               // (a due-masked solve: the number of due instances it counted)
-constexpr int kHdrCall = 30;   // cnt[kHdrCall]: a due-masked solve's whole batch (0: an unmasked solve)
-static_assert(1 + kLists <= kDeq && kDeq + kLists <= kHdrCall && kHdrCall < kHdrBatch && kHdrBatch < kHdr,
-              "list lengths, dequeue counters and the batch tag fit the header");
 inline size_t work_ints(int max_batch) { return 2 * kHdr + kLists * (size_t)max_batch; }
 // Side streams and events of one handle: the wider size classes run concurrently with class 1
 // (they are latency-bound: few instances, long serial solves). Three side streams (the third
@@ -174,18 +162,6 @@ constexpr uint8_t kHandoffStatus = 0xFE;
 hipError_t launch_tail(const float* d_recs, const KParams& P, float* d_forces, uint8_t* d_status,
                        int32_t* d_iters, const int* in_list, const int* in_count, int* ovf_list,
                        int* ovf_count, int grid, hipStream_t stream, int rest_grid = 0);
-// the reduced sizes the tail class takes from the 80-column wide class: 64 < n <= 72 at N <= 10
-// (the horizons without the fp64 refinement of the wide classes; with the refinement switched
-// off, cmpc_batch_set_refine(0), the longer horizons keep the 80-column class, whose parity the
-// refine-off tests cover)
-__host__ __device__ inline bool tail_class(const KParams& P, int n) {
-  return !P.refine && P.N <= 10 && n > 64 && n <= 72;
-}
-// the tail class in its self-classifying form (no classify list): grid workgroups scan the batch
-// in chunks of `chunk` instances and solve its tail-class instances, launched ahead of class 1
-hipError_t launch_tail_self(const float* d_recs, int batch, const KParams& P, float* d_forces, uint8_t* d_status,
-                            int32_t* d_iters, int* ovf_list, int* ovf_count, int grid, int chunk,
-                            hipStream_t stream);
 hipError_t launch_single(const float* d_rec, int n, const KParams& P, float* d_forces,
                          uint8_t* d_status, int32_t* d_iters, const int* d_one, hipStream_t stream,
                          bool allow_tail = true);
@@ -226,7 +202,7 @@ hipError_t launch_condense(const float* d_recs, int batch, const KParams& P, flo
 hipError_t launch_evaluate(const float* d_recs, const float* d_forces, int batch, const KParams& P,
                            double alpha, const double* ib64, float* d_xpred, double* d_cert,
                            hipStream_t stream, const double* inst_rows = nullptr);
-// per-instance table (cmpc_launch.hip). check: *d_bad += the number of rows that
+// per-instance table (cmpc_inst_table.hip). check: *d_bad += the number of rows that
 // cmpc_batch_set_model or cmpc_batch_set_params would refuse (d_bad zeroed by the caller);
 // convert: the kernel-side entries and the snapshot of the rows, formed as make_kmodel and
 // make_kparams form the handle's values on the host
