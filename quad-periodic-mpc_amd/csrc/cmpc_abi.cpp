@@ -77,9 +77,7 @@ struct cmpc_batch {
   int ev_every = 1, ev_solves = 0;  // events on every ev_every-th solve (cmpc_batch_enable_timing_every)
 };
 
-#ifndef CMPC_REFINE_FROM_N
-#define CMPC_REFINE_FROM_N 11  // first horizon whose wide classes refine (diagnostic builds move it)
-#endif
+constexpr int CMPC_REFINE_FROM_N = 11;  // first horizon whose wide classes refine
 
 // Side streams come from a process-wide pool and go back to it when a handle is destroyed; a new
 // handle takes the oldest free set. The runtime maps streams onto a few hardware queues

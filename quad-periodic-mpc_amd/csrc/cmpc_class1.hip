@@ -16,7 +16,7 @@
 //     symmetric, pivot column k is "register slot[k] of every lane": ONE ds_write_b32 per step
 //     publishes it, and the broadcast reads are ds_read_b128; the Cholesky's trailing sweep and
 //     the active set's reflection take the broadcast from lane c's register instead, as 4x4x1
-//     MFMA outer products with the A-operand broadcast (CMPC_C1_MFMA);
+//     MFMA outer products with the A-operand broadcast;
 //   * J = L^-T is solved left-looking inside the factorisation's pair steps: the stored columns
 //     are -L's, lane v keeps x_j = J[v][j] in the registers of the finished H columns, and each
 //     step adds the row sums over the finished columns (16-B broadcasts, four rows per read);
@@ -30,86 +30,12 @@
 
 #include "cmpc_common.h"
 
-#ifndef CMPC_W1_WAVES_60  // the 60-wide build's occupancy target (A/B builds; 5 measured config 3 -18 %, r04_q)
-#define CMPC_W1_WAVES_60 4
-#endif
-#ifndef CMPC_W1_WAVES_PER_EU
-#define CMPC_W1_WAVES_PER_EU 4
-#endif
-// Cholesky sweep chunks (of every 4) whose column broadcast goes through v_readlane instead of
-// the LDS (see the Cholesky stage)
-#ifndef CMPC_C1_RL
-#define CMPC_C1_RL 0
-#endif
-// Active-set trips after which a wave raises its issue priority (0: never): the instances with
-// many trips set the end of a batch that does not fill the GPU many times over
-#ifndef CMPC_TRIP_PRIO_AT
-#define CMPC_TRIP_PRIO_AT 0
-#endif
-#ifndef CMPC_C1_TRIP_PRIO
-#define CMPC_C1_TRIP_PRIO 2
-#endif
+// occupancy targets of the 60-wide and the 64-wide build (5 for the 60-wide measured config 3
+// -18 %, r04_q)
+constexpr int CMPC_W1_WAVES_60 = 4;
+constexpr int CMPC_W1_WAVES_PER_EU = 4;
 // chunks per group of the software-pipelined vector sweeps (piped_sweep)
-#ifndef C1_PIPE_GRP
-#define C1_PIPE_GRP 4
-#endif
-// Cholesky two pivots per step (rank-2 sweeps); 0: one pivot per step
-#ifndef CMPC_C1_CHOL2
-#define CMPC_C1_CHOL2 1
-#endif
-// J = L^-T left-looking inside the Cholesky's pair steps (no separate J pass; CMPC_C1_CHOL2 only):
-// 2 four rows per 16-B read (config 3 +2 %, 32768 instances +2 %, 4096 +1.5 %, profiles/r06_s7),
-// 1 two rows per 8-B read (-3 to -4 %), 0 the separate right-looking pass after the factorisation
-#ifndef CMPC_C1_FUSEDJ
-#define CMPC_C1_FUSEDJ 2
-#endif
-// (form 2) the J row sums' column loads software-pipelined one group ahead: config 3 +0.9 /
-// +1.3 %, 4096 +0.6 / +0.8 %, 32768 -0.2 % (profiles/r06_s9/lib_ab.log); 0: one group at a time
-#ifndef CMPC_C1_JPIPE
-#define CMPC_C1_JPIPE 1
-#endif
-// the active set's row-long dot products (z = J2 d2, |d2|^2, J_v . w) as two interleaved FMA
-// chains (dot4x2) instead of one (A/B)
-#ifndef CMPC_C1_DOT2
-#define CMPC_C1_DOT2 0
-#endif
-#if CMPC_C1_DOT2
-#define C1_DOT dot4x2
-#else
-#define C1_DOT dot4
-#endif
-// (form 2) x = -J y accumulated inside the factorisation (two FMAs per pair step with the
-// step's border values) instead of an LDS sweep after it: config 3 +0.8 / +1.8 %, 4096 +0.3 /
-// +0.9 %, 32768 -0.4 / +1.4 % (profiles/r06_s12/lib_ab.log)
-#ifndef CMPC_C1_XUNC
-#define CMPC_C1_XUNC 1
-#endif
-// Row sweeps as broadcast outer products on the matrix pipe (v_mfma_f32_4x4x1_16b_f32, cbsz 4):
-// every sweep FMA is slot[c] += (this lane's coefficient) x (a value lane c holds), and with
-// A = the lane-natural column register, B = the coefficient and abid = c / 4 one MFMA does
-//   slot[c + i] (lane v) += A(lane c + i) B(lane v),  i = 0..3,
-// a whole sweep chunk with no LDS broadcast and no VALU FMA (layout and rounding checked by
-// tools/cmpc_mfma_probe.cpp). MFMAs ignore EXEC: each sits in wave-uniform control flow.
-// The MFMA rounds as one fmaf, denormals included, and every stage keeps each element's order
-// of additions, so all of them give the LDS form's forces bit for bit.
-// 1: the Cholesky's rank-2 trailing sweep (config 3 +2.6 % over 0); 2: also the active set's
-// reflection update (0 to +1.1 % over 1 per rotation, separated in two sessions of three); 3:
-// also the fused J's row sums (does not separate from 2); 0: the LDS-broadcast FMAs
-// (profiles/r12_mfma)
-#ifndef CMPC_C1_MFMA
-#define CMPC_C1_MFMA 2
-#endif
-#if CMPC_C1_MFMA && !(CMPC_C1_CHOL2 && CMPC_C1_FUSEDJ)
-#error "CMPC_C1_MFMA needs the pair-step Cholesky with the fused J (CMPC_C1_CHOL2, CMPC_C1_FUSEDJ)"
-#endif
-// Tables with exactly two stance feet at every step (trot, the deployed gait) and 6 N <= NV:
-// reduced column 6 i + 3 s + a of step i's s-th stance foot is a compile-time register index, so
-// lane v condenses its whole row (both sides of the diagonal, from its own chain continued below
-// step k_v) straight into slot[], with no H exchange through the LDS and no row load
-// (DESIGN.md §4.1 round 13). 0: every table takes the exchange.
-#ifndef CMPC_C1_STATIC2
-#define CMPC_C1_STATIC2 1
-#endif
+constexpr int C1_PIPE_GRP = 4;
 
 // Phase profiler (diagnostic builds only, -DCMPC_PHASE_PROF): lane 0 of every solved instance
 // adds the s_memtime cycles spent in each stage to g_c1_phase (scripts/phase_prof.py).
@@ -210,7 +136,6 @@ struct SharedC1 {
   // sixteen one-wave workgroups (four waves per SIMD) fit a CU's 160 KB
   union {
     float BdtT[12][16];    // prep + condensation: Bdt transposed
-    float ibuf[NL];        // Cholesky + J: 1 / sqrt(d_k) of pivot k
     struct {               // active set
       float bufA[NL], bufB[NL];  // published J rows ia (bufA) and iz (bufB + 16, running into cs)
       float cs[2 * NL];    // Givens (c, s) per column pair
@@ -232,7 +157,15 @@ __device__ __forceinline__ void lsync() {
 
 __device__ __forceinline__ float fdiv(float a, float b) { return a * fast_rcp(b); }
 
-#if CMPC_C1_MFMA
+// Row sweeps as broadcast outer products on the matrix pipe (v_mfma_f32_4x4x1_16b_f32, cbsz 4):
+// every sweep FMA is slot[c] += (this lane's coefficient) x (a value lane c holds), and with
+// A = the lane-natural column register, B = the coefficient and abid = c / 4 one MFMA does
+//   slot[c + i] (lane v) += A(lane c + i) B(lane v),  i = 0..3,
+// a whole sweep chunk with no LDS broadcast and no VALU FMA (layout and rounding checked by
+// tools/cmpc_mfma_probe.cpp). MFMAs ignore EXEC: each sits in wave-uniform control flow.
+// The MFMA rounds as one fmaf, denormals included, and each sweep keeps every element's order of
+// additions. Two sweeps run this way: the Cholesky's rank-2 trailing sweep and the active set's
+// reflection update (profiles/r12_mfma).
 typedef float f4m __attribute__((ext_vector_type(4)));
 // one sweep chunk: x_i (this lane) += col(lane C + i) * coef (this lane), i = 0..3 (C = 0 mod 4)
 template <int C>
@@ -246,7 +179,6 @@ __device__ __forceinline__ void mfma_chunk(float col, float coef, float& x0, flo
   x2 = acc[2];
   x3 = acc[3];
 }
-#endif
 
 // Register pin: forces every row element to be materialised at this point. Without it LLVM sinks
 // the right-looking updates of slot[c] down to the step that first reads slot[c] (turning the
@@ -296,17 +228,7 @@ __device__ __forceinline__ float pick_col(const float (&x)[MA], int q) {
   }
 }
 
-// Scheduling fence inside long unrolled LDS->FMA sweeps: without it the scheduler issues every
-// ds_read_b128 of a row up front (64 extra live VGPRs on top of the 65-slot row).
-#ifndef CMPC_FENCE_COLS
-#define CMPC_FENCE_COLS 16
-#endif
-#define CMPC_SWEEP_FENCE(c)                                                                  \
-  do {                                                                                       \
-    if (((c) & (CMPC_FENCE_COLS - 1)) == CMPC_FENCE_COLS - 4) __builtin_amdgcn_sched_barrier(0); \
-  } while (0)
-
-// POFF, OOFF (CMPC_C1_STATIC2): the byte offsets of the kernel's KParams and of its three output
+// POFF, OOFF: the byte offsets of the kernel's KParams and of its three output
 // pointers (forces, status, iters, one after the other) in its argument segment. The outputs are
 // then read where the instance is written out (karg_late), not held in six SGPRs from kernel
 // entry, and fout / st_out / it_out are not used.
@@ -412,17 +334,19 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
   // ---- condensation: lane v builds H[v][w] for w >= v into packed P, and its gradient g_v
   const bool real = v < n;
   float gv;
-#if CMPC_C1_STATIC2
   float slot[NV + 1];
-  // two stance feet at every step and every step inside the row: then n = 6 N, k_v = v / 6 and
-  // the column of entry (i, s, a) is 6 i + 3 s + a. From the stance ballots alone (wave-uniform,
-  // the record's property: the same path in every batch and launch form)
+  // Tables with exactly two stance feet at every step (trot, the deployed gait) and 6 N <= NV:
+  // then n = 6 N, k_v = v / 6 and reduced column 6 i + 3 s + a of step i's s-th stance foot is a
+  // compile-time register index, so lane v condenses its whole row (both sides of the diagonal,
+  // from its own chain continued below step k_v) straight into slot[], with no H exchange through
+  // the LDS and no row load. Every other table takes the exchange.
+  // Decided from the stance ballots alone (wave-uniform, the record's property: the same path in
+  // every batch and launch form)
   bool st2 = 6 * N <= NV;
   static_for<0, NV / 6>([&](auto IC) {
     constexpr int i = decltype(IC)::value;
     if (i < N) st2 = st2 && (__builtin_popcount(step_mask(msk0, msk1, i)) == 2);
   });
-#endif
   {
     const int kv = real ? sh.varblk[v] : 0;
     const int cv = real ? sh.varcol[v] : 0;
@@ -438,7 +362,6 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
     float z[13];
 #pragma unroll
     for (int j = 0; j < 13; j++) z[j] = 0.f;
-#if CMPC_C1_STATIC2
     if (st2) {
       // the model's uniform values in SGPRs for the unrolled steps: the row is live beside them
       Model ms;
@@ -523,9 +446,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       });
       slot[NV] = gv;
       C1_MARK(1);
-    } else
-#endif
-    {
+    } else {
       const int myrow = G::tri(v);
       const float alpha2 = cost_alpha2<INST>(P, ie);
       for (int i = N - 1; i >= 0; i--) {
@@ -550,12 +471,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
   }
 
   // ---- row v of H into registers (full symmetric; identity padding for v >= n) ----------
-#if CMPC_C1_STATIC2
-  if (!st2)  // (the two-stance rows are in slot[] already)
-#else
-  float slot[NV + 1];
-#endif
-  {
+  if (!st2) {  // (the two-stance rows are in slot[] already)
     C1_MARK(1);
     const int vv = (v < NV) ? v : 0;  // lanes without a row read row 0 (and keep a zero row)
     const int myrow = G::tri(vv);
@@ -570,32 +486,26 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
     lsync();
   }
 
-  // ---- bordered Cholesky [H | g]: raw column k = slot[k] of every lane -> P row k ----------
-  // Look-ahead: step k publishes column k+1 (and takes its pivot d_{k+1} and border g_{k+1})
-  // as soon as the sweep chunk holding slot[k+1] is updated, so nothing of step k+1's setup
-  // waits on the LDS. The broadcast of column k to every lane is split between two paths that
-  // run concurrently: CMPC_C1_RL of every 4 sweep chunks take it by v_readlane into SGPRs (FMA
-  // with an SGPR operand, VALU only), the others by ds_read_b128 broadcasts of the stored
-  // column (the LDS delivers 4 B per lane per cycle; with every chunk on it the sweep is LDS
-  // bound). The stored columns also feed J = L^-T below.
-  int status = CMPC_OK;
-  float my_inv = 1.f;
-#if CMPC_C1_CHOL2
-  // Two pivots per step (k even, k+1): one rank-2 sweep over the raw column k and column k+1
-  // as it is after step k,
+  // ---- bordered Cholesky [H | g] with J = L^-T and x = -J y solved inside it ----------------
+  // Column k of the working matrix is slot[k] of every lane. Two pivots per step (k even, k+1):
+  // one rank-2 sweep over the raw column k and column k+1 as it is after step k,
   //   slot[c] += a0 P_k[c] + a1 P_k+1[c]  (c >= k+2),  a0 = -H[v][k] / d_k,  a1 = -s1 / d_k+1,
   //   s1 = H[v][k+1] - beta H[v][k],  beta = H[k+1][k] / d_k,  d_k+1 = H[k+1][k+1] - beta H[k+1][k]
-  // so the 60 serial steps (pivot, broadcast, LDS round trip) become 30 with the same FMA count.
+  // so NV / 2 serial steps (pivot, broadcast) do the work of NV. The sweep takes both columns
+  // from the registers of the lanes that own them, as MFMA outer products (mfma_chunk); the
+  // columns are also stored to P (one ds_write_b32 each), where only the J sums read them.
   // Look-ahead: as soon as the sweep chunk holding columns k+2, k+3 is updated, the step takes
   // their pivot data by readlane, forms the next step's beta / d / 1/sqrt(d), and publishes
   // column k+2 and the corrected column k+3; so the next step starts on its sweep at once. The
   // stored columns (raw even, corrected odd) are what J = L^-T needs. Odd n: the last step's
   // second pivot is the identity padding row (H[n][n] = 1, no coupling).
+  // Each pair step then finishes rows k, k+1 of J left-looking from the stored columns, and adds
+  // their terms to x = -J y, so the stage ends with J in slot[0..NV) and the unconstrained
+  // minimiser in xunc.
+  int status = CMPC_OK;
   float i0n = 1.f, betan = 0.f, i1n = 1.f, g0n = 0.f, g1n = 0.f;
-#if CMPC_C1_MFMA
   // the two published columns as look leaves them, one element per lane: the MFMA sweep's A operand
   float pub0n = 0.f, pub1n = 0.f;
-#endif
   // pivot data of the step at columns (j, j+1) from the current rows, and the publish of both
   // columns (lanes >= the columns' chunk start)
   auto look = [&](auto JJ) {
@@ -613,63 +523,35 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
     g0n = rl(slot[NV], j);
     g1n = fmaf(-betan, g0n, rl(slot[NV], j1));  // border of row j+1 after step j
     const float s1 = fmaf(-slot[j], betan, slot[j1]);
-#if CMPC_C1_FUSEDJ
     // the factor's columns themselves, negated: P'_j = -L[:, j] = -slot[j] / sqrt(d_j) (and the
     // corrected column j+1 likewise), so the sweep and the left-looking J both read them as they are
     g0n = -g0n * i0n;
     g1n = -g1n * i1n;
-#if CMPC_C1_MFMA
     // the sweep takes the columns from these registers; the stores feed only the J sums, which
     // order themselves after them (lsync ahead of the sums)
     pub0n = (v >= j) ? -slot[j] * i0n : 0.f;
     pub1n = (v >= j1) ? -s1 * i1n : 0.f;
     if (v >= cj && v < NV) sh.P[G::prow(j) + v - cj] = pub0n;
     if (v >= cj1 && v < NV) sh.P[G::prow(j1) + v - cj1] = pub1n;
-#else
-    if (v >= cj && v < NV) sh.P[G::prow(j) + v - cj] = (v >= j) ? -slot[j] * i0n : 0.f;
-    if (v >= cj1 && v < NV) sh.P[G::prow(j1) + v - cj1] = (v >= j1) ? -s1 * i1n : 0.f;
-#endif
-#else
-    if (v >= cj && v < NV) sh.P[G::prow(j) + v - cj] = (v >= j) ? slot[j] : 0.f;
-    if (v >= cj1 && v < NV) sh.P[G::prow(j1) + v - cj1] = (v >= j1) ? s1 : 0.f;
-#endif
-#if !CMPC_C1_MFMA
-    lsync();
-#endif
     }
   };
   if (n > 0) look(std::integral_constant<int, 0>{});
-  float jc2 = 0.f, jc3 = 0.f;  // (CMPC_C1_FUSEDJ 2) rows k+2, k+3 of J's sums, carried one pair step
-  (void)jc2; (void)jc3;
-  // (CMPC_C1_XUNC) x = -J y accumulated as J's entries are solved: y_k = -g0 of pair step k (the
-  // border of row k after the pivots before it, scaled by -1/sqrt(d_k) in look)
+  float jc2 = 0.f, jc3 = 0.f;  // rows k+2, k+3 of J's sums, carried one pair step
+  // x = -J y accumulated as J's entries are solved: y_k = -g0 of pair step k (the border of row k
+  // after the pivots before it, scaled by -1/sqrt(d_k) in look)
   float xunc = 0.f;
-  (void)xunc;
   static_for<0, NV / 2>([&](auto KB) {
     constexpr int k = 2 * decltype(KB)::value;
     constexpr int k1 = k + 1, k2 = k + 2;
-    constexpr int c0 = k & ~3, c1 = k1 & ~3, c2 = k2 & ~3;
-    constexpr int rk = G::prow(k), rk1 = G::prow(k1);
+    constexpr int c2 = k2 & ~3;
     if (k < n) {
       const float i0 = i0n, beta = betan, i1 = i1n, g0 = g0n, g1 = g1n;
-#if CMPC_C1_FUSEDJ
-      if (v == k) my_inv = i0;
-      if (v == k1) my_inv = i1;
       const float s0 = slot[k];
       const float s1 = fmaf(-s0, beta, slot[k1]);
       // row v of L in columns k, k+1 (the sweep adds l_vk P'_k + l_vk+1 P'_k+1, P' = -L)
       const float a0 = (v > k) ? s0 * i0 : 0.f;
       const float a1 = (v > k1) ? s1 * i1 : 0.f;
-#else
-      if (v == k) { my_inv = i0; sh.u.ibuf[k] = i0; }
-      if (v == k1) { my_inv = i1; sh.u.ibuf[k1] = i1; }
-      const float s0 = slot[k];
-      const float s1 = fmaf(-s0, beta, slot[k1]);
-      const float a0 = (v > k) ? -s0 * (i0 * i0) : 0.f;
-      const float a1 = (v > k1) ? -s1 * (i1 * i1) : 0.f;
-#endif
       slot[NV] = fmaf(a1, g1, fmaf(a0, g0, slot[NV]));
-#if CMPC_C1_MFMA
       // slot[c] += a0 P'_k[c] + a1 P'_k+1[c] with P'[c] taken from lane c's register. The chunk
       // with columns k+2, k+3 takes both pivots first (the look-ahead follows it); the others
       // all of pivot k, then all of pivot k+1, so that two MFMAs on one accumulator sit a
@@ -691,20 +573,6 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
         });
       }
       lsync();  // the J sums below read the stored columns
-#else
-      static_for<c2 / 4, NV / 4>([&](auto JC) {
-        constexpr int c = 4 * decltype(JC)::value;
-        const float4 r0 = *reinterpret_cast<const float4*>(&sh.P[rk + c - c0]);
-        const float4 r1 = *reinterpret_cast<const float4*>(&sh.P[rk1 + c - c1]);
-        axpy4(a0, r0, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
-        axpy4(a1, r1, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
-        if constexpr (k2 < NV && c == c2) {
-          if (k2 < n) look(std::integral_constant<int, k2>{});  // columns k+2, k+3 are final
-        }
-        CMPC_SWEEP_FENCE(c);
-      });
-#endif
-#if CMPC_C1_FUSEDJ == 2
       // J = L^-T, left-looking, four rows per 16-B read: at k = 0 mod 4 the sums of rows k..k+3
       // over every finished column j < k (one ds_read_b128 broadcast of P'_j[k..k+3] per column,
       // four columns per group, the next group's loads issued before this group's FMAs, two
@@ -714,35 +582,6 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       if constexpr ((k & 3) == 0) {
         f2v t0 = {(v == k) ? 1.f : 0.f, 0.f}, t1 = {(v == k1) ? 1.f : 0.f, 0.f};
         f2v t2 = {(v == k + 2) ? 1.f : 0.f, 0.f}, t3 = {(v == k + 3) ? 1.f : 0.f, 0.f};
-#if CMPC_C1_MFMA >= 3
-        // the same sums on the matrix pipe: per finished column q one lane-natural 4-B read of
-        // the stored column (lane c gets P'_q[c]; only lanes k..k+3 are selected, abid = k / 4)
-        // and one MFMA t_i += P'_q[k + i] x_q, i = 0..3, in place of a 16-B broadcast and four
-        // FMAs. Two accumulator tuples, even columns in one and odd in the other, as the .x / .y
-        // chains above: consecutive MFMAs do not chain and every sum keeps its order.
-        {
-          f4m te = {t0.x, t1.x, t2.x, t3.x}, to = {0.f, 0.f, 0.f, 0.f};
-          const int vc = (v < NV) ? v : NV - 1;  // (lanes without a row stay inside row q)
-          piped_sweep<0, k, 2>(
-              [&](auto C) {
-                constexpr int q = decltype(C)::value;  // columns q .. q+3 (4 | k), rows from q & ~3 = q
-                return float4{sh.P[G::prow0(q) + vc], sh.P[G::prow0(q + 1) + vc],
-                              sh.P[G::prow0(q + 2) + vc], sh.P[G::prow0(q + 3) + vc]};
-              },
-              [&](auto C, float4 l) {
-                constexpr int q = decltype(C)::value;
-                te = __builtin_amdgcn_mfma_f32_4x4x1f32(l.x, slot[q], te, 4, k / 4, 0);
-                to = __builtin_amdgcn_mfma_f32_4x4x1f32(l.y, slot[q + 1], to, 4, k / 4, 0);
-                te = __builtin_amdgcn_mfma_f32_4x4x1f32(l.z, slot[q + 2], te, 4, k / 4, 0);
-                to = __builtin_amdgcn_mfma_f32_4x4x1f32(l.w, slot[q + 3], to, 4, k / 4, 0);
-              });
-          t0 = {te[0], to[0]};
-          t1 = {te[1], to[1]};
-          t2 = {te[2], to[2]};
-          t3 = {te[3], to[3]};
-        }
-#else
-#if CMPC_C1_JPIPE
         // loads of the next column group issued before this group's FMAs (one group ahead)
         piped_sweep<0, k, 1>(
             [&](auto C) {
@@ -755,36 +594,20 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
             [&](auto C, F4x4 l) {
               constexpr int q = decltype(C)::value;
               const float4 la = l.a, lb = l.b, lc = l.c, ld = l.d;
-#else
-        static_for<0, k / 4>([&](auto QC) {
-          constexpr int q = 4 * decltype(QC)::value;  // columns q .. q+3 (4 | k)
-          const float4 la = *reinterpret_cast<const float4*>(&sh.P[G::prow(q) + k - q]);
-          const float4 lb = *reinterpret_cast<const float4*>(&sh.P[G::prow(q + 1) + k - q]);
-          const float4 lc = *reinterpret_cast<const float4*>(&sh.P[G::prow(q + 2) + k - q]);
-          const float4 ld = *reinterpret_cast<const float4*>(&sh.P[G::prow(q + 3) + k - q]);
-#endif
-          t0.x = fmaf(slot[q], la.x, t0.x); t1.x = fmaf(slot[q], la.y, t1.x);
-          t2.x = fmaf(slot[q], la.z, t2.x); t3.x = fmaf(slot[q], la.w, t3.x);
-          t0.y = fmaf(slot[q + 1], lb.x, t0.y); t1.y = fmaf(slot[q + 1], lb.y, t1.y);
-          t2.y = fmaf(slot[q + 1], lb.z, t2.y); t3.y = fmaf(slot[q + 1], lb.w, t3.y);
-          t0.x = fmaf(slot[q + 2], lc.x, t0.x); t1.x = fmaf(slot[q + 2], lc.y, t1.x);
-          t2.x = fmaf(slot[q + 2], lc.z, t2.x); t3.x = fmaf(slot[q + 2], lc.w, t3.x);
-          t0.y = fmaf(slot[q + 3], ld.x, t0.y); t1.y = fmaf(slot[q + 3], ld.y, t1.y);
-          t2.y = fmaf(slot[q + 3], ld.z, t2.y); t3.y = fmaf(slot[q + 3], ld.w, t3.y);
-#if CMPC_C1_JPIPE
+              t0.x = fmaf(slot[q], la.x, t0.x); t1.x = fmaf(slot[q], la.y, t1.x);
+              t2.x = fmaf(slot[q], la.z, t2.x); t3.x = fmaf(slot[q], la.w, t3.x);
+              t0.y = fmaf(slot[q + 1], lb.x, t0.y); t1.y = fmaf(slot[q + 1], lb.y, t1.y);
+              t2.y = fmaf(slot[q + 1], lb.z, t2.y); t3.y = fmaf(slot[q + 1], lb.w, t3.y);
+              t0.x = fmaf(slot[q + 2], lc.x, t0.x); t1.x = fmaf(slot[q + 2], lc.y, t1.x);
+              t2.x = fmaf(slot[q + 2], lc.z, t2.x); t3.x = fmaf(slot[q + 2], lc.w, t3.x);
+              t0.y = fmaf(slot[q + 3], ld.x, t0.y); t1.y = fmaf(slot[q + 3], ld.y, t1.y);
+              t2.y = fmaf(slot[q + 3], ld.z, t2.y); t3.y = fmaf(slot[q + 3], ld.w, t3.y);
             });
-#else
-          __builtin_amdgcn_sched_barrier(0);
-        });
-#endif
-#endif  // CMPC_C1_MFMA >= 3
         const float hk = sh.P[G::prow(k) + k1 - (k & ~3)];  // -L[k+1][k]
         const float xk = (t0.x + t0.y) * i0;
         slot[k] = xk;
         slot[k1] = fmaf(xk, hk, t1.x + t1.y) * i1;
-#if CMPC_C1_XUNC
         xunc = fmaf(slot[k1], g1, fmaf(xk, g0, xunc));
-#endif
         jc2 = t2.x + t2.y;
         jc3 = t3.x + t3.y;
         asm volatile("" : "+v"(jc2), "+v"(jc3));
@@ -798,176 +621,17 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
         const float xk = e0 * i0;
         slot[k] = xk;
         slot[k1] = fmaf(xk, hk, e1) * i1;
-#if CMPC_C1_XUNC
         xunc = fmaf(slot[k1], g1, fmaf(xk, g0, xunc));
-#endif
       }
-#elif CMPC_C1_FUSEDJ
-      // J = L^-T, left-looking: lane v solves L x = e_v, x_k = (d_vk - sum_{j<k} L[k][j] x_j) / L[k][k];
-      // x_j (j < k) sit in the registers of the factor's finished columns, L[k][j], L[k+1][j] are
-      // one 8-B broadcast of the stored column j (k even, rows start 16-B aligned), two interleaved
-      // accumulators per row keep the FMA chains short. Every column of the factor is thus read
-      // once more here instead of in a separate pass of 30 serial steps after the factorisation.
-      {
-        float e0 = (v == k) ? 1.f : 0.f, e1 = (v == k1) ? 1.f : 0.f, o0 = 0.f, o1 = 0.f;
-        static_for<0, k>([&](auto JJ) {
-          constexpr int j = decltype(JJ)::value;
-          const float2 lj = *reinterpret_cast<const float2*>(&sh.P[G::prow(j) + k - (j & ~3)]);
-          if constexpr ((j & 1) == 0) {
-            e0 = fmaf(slot[j], lj.x, e0);
-            e1 = fmaf(slot[j], lj.y, e1);
-          } else {
-            o0 = fmaf(slot[j], lj.x, o0);
-            o1 = fmaf(slot[j], lj.y, o1);
-          }
-          if constexpr ((j & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-        });
-        const float hk = sh.P[G::prow(k) + k1 - (k & ~3)];  // -L[k+1][k]
-        const float xk = (e0 + o0) * i0;
-        slot[k] = xk;
-        slot[k1] = fmaf(xk, hk, e1 + o1) * i1;
-      }
-#endif
       pin(slot);
     }
   });
-#else
-  float dnext = 1.f, gnext = 0.f;
-  if (n > 0) {
-    if (v < NV) sh.P[G::prow(0) + v] = slot[0];
-    dnext = rl(slot[0], 0);
-    gnext = rl(slot[NV], 0);
-    lsync();
-  }
-  static_for<0, NV>([&](auto KC) {
-    constexpr int k = decltype(KC)::value;
-    constexpr int c0 = k & ~3;
-    constexpr int rk = G::prow(k);
-    constexpr int k1 = k + 1;
-    constexpr int c1 = k1 & ~3;
-    if (k < n) {
-      float d = dnext;
-      const float gk = gnext;
-      if (!(d > 0.f)) { status = CMPC_NOT_PD; d = 1e-30f; }
-      const float inv = __builtin_amdgcn_rsqf(d);  // d is a normal positive pivot
-      if (v == k) { my_inv = inv; sh.u.ibuf[k] = inv; }
-      const float colk = slot[k];  // lane c holds the raw column entry of row c
-      const float a = (v > k) ? -colk * (inv * inv) : 0.f;
-      slot[NV] = fmaf(a, gk, slot[NV]);
-      static_for<c0 / 4, NV / 4>([&](auto JC) {
-        constexpr int c = 4 * decltype(JC)::value;
-        if constexpr (((c / 4) & 3) < CMPC_C1_RL) {
-          // four readlanes into distinct SGPRs ahead of the four FMAs: a readlane's SGPR
-          // result needs two wait states before a VALU may read it
-          float s4[4];
-          static_for<0, 4>([&](auto EC) {
-            constexpr int cc = c + decltype(EC)::value;
-            s4[EC] = (cc >= k) ? rl(colk, cc) : 0.f;
-          });
-          asm volatile("" : "+s"(s4[0]), "+s"(s4[1]), "+s"(s4[2]), "+s"(s4[3]));
-          static_for<0, 4>([&](auto EC) {
-            constexpr int cc = c + decltype(EC)::value;
-            if constexpr (cc >= k) slot[cc] = fmaf(a, s4[EC], slot[cc]);
-          });
-        } else {
-          const float4 r4 = *reinterpret_cast<const float4*>(&sh.P[rk + c - c0]);
-          axpy4(a, r4, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
-        }
-        if constexpr (k1 < NV && c == c1) {
-          if (k1 < n) {  // publish column k+1 (final after this chunk)
-            constexpr int rk1 = G::prow(k1);
-            if (v >= c1 && v < NV) sh.P[rk1 + v - c1] = (v >= k1) ? slot[k1] : 0.f;
-            dnext = rl(slot[k1], k1);
-            gnext = rl(slot[NV], k1);
-            lsync();
-          }
-        }
-        CMPC_SWEEP_FENCE(c);
-      });
-      pin(slot);
-    }
-  });
-#endif
-  const float yv = (v < n) ? slot[NV] * my_inv : 0.f;  // L y = g
   lsync();
   C1_MARK(2);
-
-  // ---- J = L^-T: lane v solves L x = e_v (column v of L^-1 = row v of J) -----------------
-#if CMPC_C1_CHOL2 && CMPC_C1_FUSEDJ
-  // done inside the factorisation above; the columns past n are the identity rows' e_v already
-#else
-  static_for<0, NV>([&](auto C) {
-    constexpr int c = decltype(C)::value;
-    slot[c] = (c == v) ? 1.f : 0.f;
-  });
-#endif
-#if CMPC_C1_CHOL2 && CMPC_C1_FUSEDJ
-#elif CMPC_C1_CHOL2
-  // two columns per step, as the factorisation: x_k, then x_k+1 after column k's term, then one
-  // rank-2 sweep over the stored columns k, k+1 (the odd-n padding column is the identity)
-  static_for<0, NV / 2>([&](auto KB) {
-    constexpr int k = 2 * decltype(KB)::value;
-    constexpr int k1 = k + 1, c2 = (k + 2) & ~3;
-    constexpr int c0 = k & ~3, c1 = k1 & ~3;
-    constexpr int rk = G::prow(k), rk1 = G::prow(k1);
-    if (k < n) {  // P and ibuf are read-only here: no per-step LDS ordering needed
-      const float i0 = sh.u.ibuf[k], i1 = sh.u.ibuf[k1];
-      const float h = sh.P[rk + k1 - c0];  // L[k+1][k] sqrt(d_k)
-      const float x0 = slot[k] * i0;
-      const float x1 = fmaf(-h * i0, x0, slot[k1]) * i1;
-      const float a0 = -x0 * i0, a1 = -x1 * i1;
-#pragma unroll
-      for (int c = c2; c < NV; c += 4) {
-        const float4 r0 = *reinterpret_cast<const float4*>(&sh.P[rk + c - c0]);
-        const float4 r1 = *reinterpret_cast<const float4*>(&sh.P[rk1 + c - c1]);
-        axpy4(a0, r0, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
-        axpy4(a1, r1, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
-        CMPC_SWEEP_FENCE(c);
-      }
-      slot[k] = x0;
-      slot[k1] = x1;
-      pin(slot);
-    }
-  });
-#else
-  static_for<0, NV>([&](auto KC) {
-    constexpr int k = decltype(KC)::value;
-    constexpr int c0 = k & ~3;
-    constexpr int rk = G::prow(k);
-    if (k < n) {  // P and ibuf are read-only here: no per-step LDS ordering needed
-      const float inv = sh.u.ibuf[k];
-      const float xk = slot[k] * inv;
-      const float a = -xk * inv;
-#pragma unroll
-      for (int c = c0; c < NV; c += 4) {
-        const float4 r4 = *reinterpret_cast<const float4*>(&sh.P[rk + c - c0]);
-        axpy4(a, r4, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
-        CMPC_SWEEP_FENCE(c);
-      }
-      slot[k] = xk;
-      pin(slot);
-    }
-  });
-#endif
-
+  // (J and x = -J y are finished with the factorisation, so the profiler's phase 3 stays empty;
+  // the columns past n are the identity rows' e_v already)
   C1_MARK(3);
-  // ---- unconstrained minimiser x = -J y ----------------------------------------------------
-#if CMPC_C1_FUSEDJ == 2 && CMPC_C1_XUNC
-  (void)yv;
-  float xv = (v < n) ? xunc : 0.f;  // accumulated in the factorisation's steps
-#else
-  sh.vbuf()[v] = yv;
-  lsync();
-  f2v xacc = {0.f, 0.f};
-  piped_sweep<0, NV, C1_PIPE_GRP>(
-      [&](auto C) { return *reinterpret_cast<const float4*>(&sh.vbuf()[decltype(C)::value]); },
-      [&](auto C, float4 y4) {
-        constexpr int c = decltype(C)::value;
-        dot4(xacc, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3], y4);
-      });
-  float xv = (v < n) ? -(xacc.x + xacc.y) : 0.f;
-  lsync();
-#endif
+  float xv = (v < n) ? xunc : 0.f;
 
   // ---- Goldfarb-Idnani dual active set on the friction pyramids -----------------------------
   // One flat loop, one active-set step per trip. The QP's triangular factor R (q x q) is kept
@@ -1023,10 +687,6 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       }
       C1_SUB(0);
       if (++iters > P.max_iter + 2 * n) { status = CMPC_MAX_ITER; break; }
-#if CMPC_TRIP_PRIO_AT > 0
-      // a long solve: issue ahead of the other waves on this SIMD (shorter makespan tail)
-      if (iters == CMPC_TRIP_PRIO_AT) __builtin_amdgcn_s_setprio(CMPC_C1_TRIP_PRIO);
-#endif
       // d = J' n+ : rows ia, iz of J through LDS (dword stores: wide stores would tie the row
       // registers into tuples)
       if (v == cp.ia || v == cp.iz) {  // both rows in one pass (two lanes per store)
@@ -1055,7 +715,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
           [&](auto C) { return *reinterpret_cast<const float4*>(&sh.vbuf()[decltype(C)::value]); },
           [&](auto C, float4 m4) {
             constexpr int c = decltype(C)::value;
-            C1_DOT(zacc, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3], m4);
+            dot4(zacc, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3], m4);
           });
       float zv = zacc.x + zacc.y;
       // materialise the sum here: otherwise the FMAs sink below the back substitution loop and
@@ -1120,9 +780,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       const bool add = !zero_step && t2 <= t1;
       const bool add_u = __builtin_amdgcn_readfirstlane((int)add) != 0;
       float beta = 0.f, sigma = 0.f;  // w = d2 + sigma e_q
-#if CMPC_C1_MFMA >= 2
       float wreg = 0.f;  // w, one element per lane (0 on a drop): the reflection MFMAs' A operand
-#endif
       if (add) {
         // ---- add p: the Householder reflection I - beta w w' on columns q..n-1 maps
         // d[q..n-1] to -sgn(d_q) |d[q..n-1]| e_q; R gains the column (d[0..q-1], -sgn ts)
@@ -1131,11 +789,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
         const float sgn = (dq >= 0.f) ? 1.f : -1.f;
         beta = fast_rcp(ts * (ts + fabsf(dq)));  // 2 / (w'w)
         sigma = sgn * ts;
-#if CMPC_C1_MFMA >= 2
         wreg = (v == q) ? dq + sgn * ts : dm;
-#else
-        sh.vbuf()[v] = (v == q) ? dq + sgn * ts : dm;
-#endif
         const int offq = rcol(q);
         if (v < q) sh.P[offq + v] = dv;
         if (v == q) {
@@ -1159,9 +813,6 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
         // ---- drop active constraint kk: shift positions kk+1..q-1 down, remove column kk of
         // R and re-triangularise rows kk..q-1 (lane c rebuilds column c of R in place: every
         // read of an old entry precedes, in this wavefront's LDS order, the write reusing it)
-#if CMPC_C1_MFMA < 2
-        sh.vbuf()[v] = 0.f;
-#endif
         const int k = __builtin_amdgcn_readfirstlane(kk);
         const int ak = rli(act_reg, k);
         if (v == 0) sh.cmask[ak / 6] &= (unsigned char)~(1u << (ak % 6));
@@ -1228,20 +879,11 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
         // column pick (scalar branches on q) and one FMA instead of a second row-long dot product
         const int qs = __builtin_amdgcn_readfirstlane(q);
         const float bt = -beta * fmaf(sigma, pick_col<0, NV>(slot, qs), zv);
-#if CMPC_C1_MFMA >= 2
         // J_v[c] += bt w[c] with w[c] from lane c's register: no store of w, no broadcast reads
         static_for<0, NV / 4>([&](auto JC) {
           constexpr int c = 4 * decltype(JC)::value;
           mfma_chunk<c>(wreg, bt, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
         });
-#else
-        piped_sweep<0, NV, C1_PIPE_GRP>(
-            [&](auto C) { return *reinterpret_cast<const float4*>(&sh.vbuf()[decltype(C)::value]); },
-            [&](auto C, float4 w4) {
-              constexpr int c = decltype(C)::value;
-              axpy4(bt, w4, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
-            });
-#endif
       }
       C1_SUB(4);
       if (!add_u) {
@@ -1320,7 +962,6 @@ __global__ __launch_bounds__(64, NV == 60 ? CMPC_W1_WAVES_60 : CMPC_W1_WAVES_PER
   } else if (t >= batch) {
     return;
   }
-#if CMPC_C1_STATIC2
   using K = decltype(&cmpc_solve_c1_inst_kernel<NV>);
   using KP = KArg<2, K>;
   static_assert(std::is_same<typename KP::type, KParams>::value, "argument 2 is the KParams");
@@ -1332,10 +973,6 @@ __global__ __launch_bounds__(64, NV == 60 ? CMPC_W1_WAVES_60 : CMPC_W1_WAVES_PER
                 "arguments 3..5 are forces, status, iters");
   solve_c1<NV, KP::offset(), KArg<3, K>::offset(), true>(recs + (size_t)t * P.rec_words, P, sh, nullptr, nullptr,
                                                          nullptr, ovf_list, ovf_count, t);
-#else
-  solve_c1<NV, -1, -1, true>(recs + (size_t)t * P.rec_words, P, sh, forces + (size_t)t * P.out_cols, status + t,
-                             iters ? iters + t : nullptr, ovf_list, ovf_count, t);
-#endif
 }
 
 template <int NV>
@@ -1358,7 +995,6 @@ __global__ __launch_bounds__(64, NV == 60 ? CMPC_W1_WAVES_60 : CMPC_W1_WAVES_PER
   const unsigned hw_id = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID
   const unsigned xcc_id = __builtin_amdgcn_s_getreg((31 << 11) | 20);  // HW_REG_XCC_ID
 #endif
-#if CMPC_C1_STATIC2
   using KP = KArg<2, decltype(&cmpc_solve_c1_kernel<NV>)>;  // the KParams argument, located by this signature
   static_assert(std::is_same<typename KP::type, KParams>::value, "argument 2 is the KParams");
   using K = decltype(&cmpc_solve_c1_kernel<NV>);
@@ -1370,10 +1006,6 @@ __global__ __launch_bounds__(64, NV == 60 ? CMPC_W1_WAVES_60 : CMPC_W1_WAVES_PER
                 "arguments 3..5 are forces, status, iters");
   solve_c1<NV, KP::offset(), KArg<3, K>::offset()>(recs + (size_t)t * P.rec_words, P, sh, nullptr, nullptr,
                                                    nullptr, ovf_list, ovf_count, t);
-#else
-  solve_c1<NV>(recs + (size_t)t * P.rec_words, P, sh, forces + (size_t)t * P.out_cols, status + t,
-               iters ? iters + t : nullptr, ovf_list, ovf_count, t);
-#endif
 #ifdef CMPC_PLACE_PROF
   const unsigned long long t_end = wall_clock64();
   if (threadIdx.x == 0 && t < kPlaceMax) {

@@ -152,19 +152,11 @@ __device__ __forceinline__ int tid_opq() {
 
 // lane id (0..63) from mbcnt, opaque to the optimiser: unlike threadIdx.x (v0 at entry, which
 // has to stay live, or be spilled, to be re-read later) it needs no register between uses
-#ifndef CMPC_LANE_ASM
-#define CMPC_LANE_ASM 1
-#endif
 __device__ __forceinline__ int lane_opq() {
-#if CMPC_LANE_ASM
   // the mbcnt pair inside the asm: every call recomputes the lane id (two VALU ops) instead of
   // sharing one CSE'd value that lives across the kernel (and was spilled and reloaded per call)
   int x;
   asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(x));
-#else
-  int x = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-  asm volatile("" : "+v"(x));
-#endif
   return x;
 }
 
@@ -206,9 +198,6 @@ __device__ __forceinline__ void piped_sweep(Ld&& ld, F&& f) {
     });
   }
 }
-struct F4x2 {
-  float4 a, b;
-};
 struct F4x4 {
   float4 a, b, c, d;
 };
@@ -251,14 +240,6 @@ __device__ __forceinline__ void dot4(f2v& acc, float x0, float x1, float x2, flo
   acc.x = fmaf(x1, r.y, acc.x);
   acc.x = fmaf(x2, r.z, acc.x);
   acc.x = fmaf(x3, r.w, acc.x);
-}
-// the same with two interleaved chains (acc.x: even columns, acc.y: odd): half the dependent FMA
-// latency of a row-long dot product
-__device__ __forceinline__ void dot4x2(f2v& acc, float x0, float x1, float x2, float x3, float4 r) {
-  acc.x = fmaf(x0, r.x, acc.x);
-  acc.y = fmaf(x1, r.y, acc.y);
-  acc.x = fmaf(x2, r.z, acc.x);
-  acc.y = fmaf(x3, r.w, acc.y);
 }
 
 // single-wavefront workgroup: orders this wave's LDS traffic without an s_barrier

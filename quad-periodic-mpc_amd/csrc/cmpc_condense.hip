@@ -7,7 +7,7 @@
 // Row-owner mode (rows): every row runs its chain on down to step 0 (below its own step k_v as
 // z_i = Adt' z_{i+1}, the source term masked off) and writes its own entries on both sides of the
 // diagonal, nothing mirrored: what class 1's two-stance rows compute (cmpc_class1.hip,
-// CMPC_C1_STATIC2), here under the fp64 check of the parity hook.
+// the st2 path of solve_c1), here under the fp64 check of the parity hook.
 // CMPC_CONDENSE_INST = 1 (cmpc_condense_inst.hip, which includes this file): the per-instance build
 // for a handle with a table (cmpc_batch_set_instance_params), a kernel and a launcher of their own
 // names in a unit of their own, so that this unit compiles the shared kernel exactly as before.

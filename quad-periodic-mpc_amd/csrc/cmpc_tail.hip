@@ -34,30 +34,11 @@
 #endif
 #include "cmpc_common.h"
 
-#ifndef CMPC_TAIL_WAVES_PER_EU
-#define CMPC_TAIL_WAVES_PER_EU 3
-#endif
-#ifndef CMPC_TRIP_PRIO_AT  // active-set trips after which a wave raises its priority (0: never)
-#define CMPC_TRIP_PRIO_AT 0
-#endif
-#ifndef CMPC_TAIL_TRIP_PRIO
-#define CMPC_TAIL_TRIP_PRIO 3
-#endif
-// the active set's row-long dot products as two interleaved FMA chains (A/B)
-#ifndef CMPC_TAIL_DOT2
-#define CMPC_TAIL_DOT2 0
-#endif
-#if CMPC_TAIL_DOT2
-#define T_DOT dot4x2
-#else
-#define T_DOT dot4
-#endif
-#ifndef CMPC_TAIL_PRIO  // s_setprio of the tail classes' waves: issue ahead of the class-1 waves on their SIMDs
-#define CMPC_TAIL_PRIO 1
-#endif
-#ifndef TAIL_PIPE_GRP
-#define TAIL_PIPE_GRP 4
-#endif
+constexpr int CMPC_TAIL_WAVES_PER_EU = 3;
+// s_setprio of the tail classes' waves: issue ahead of the class-1 waves on their SIMDs
+constexpr int CMPC_TAIL_PRIO = 1;
+// chunks per group of the software-pipelined vector sweeps (piped_sweep)
+constexpr int TAIL_PIPE_GRP = 4;
 
 // Phase profiler (diagnostic builds only, -DCMPC_PHASE_PROF): lane 0 of every solved instance
 // adds the s_memtime cycles of each stage to g_t_phase (scripts/phase_prof.py --tail)
@@ -723,9 +704,6 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
         up = 0.f;
       }
       if (++iters > P.max_iter + 2 * n) { status = CMPC_MAX_ITER; break; }
-#if CMPC_TRIP_PRIO_AT > 0
-      if (iters == CMPC_TRIP_PRIO_AT) __builtin_amdgcn_s_setprio(CMPC_TAIL_TRIP_PRIO);
-#endif
       // d = J' n+: rows ia, iz of J through LDS (main rows from their lanes, tail rows from their
       // segments)
       if (v == cp.ia || v == cp.iz) {
@@ -760,8 +738,8 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
           [&](auto C) { return *reinterpret_cast<const float4*>(&sh.vbuf()[decltype(C)::value]); },
           [&](auto C, float4 m4) {
             constexpr int c = decltype(C)::value;
-            T_DOT(zacc, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3], m4);
-            T_DOT(nacc, m4.x, m4.y, m4.z, m4.w, m4);
+            dot4(zacc, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3], m4);
+            dot4(nacc, m4.x, m4.y, m4.z, m4.w, m4);
           });
       float zv = zacc.x + zacc.y, zn = nacc.x + nacc.y;
       float zt;
@@ -915,7 +893,7 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
             [&](auto C) { return *reinterpret_cast<const float4*>(&sh.vbuf()[decltype(C)::value]); },
             [&](auto C, float4 w4) {
               constexpr int c = decltype(C)::value;
-              T_DOT(tacc, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3], w4);
+              dot4(tacc, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3], w4);
             });
         const float bt = -beta * (tacc.x + tacc.y);
         float ta = 0.f;
@@ -1033,9 +1011,7 @@ __global__ __launch_bounds__(64, CMPC_TAIL_WAVES_PER_EU) void cmpc_solve_t_kerne
   static_assert(std::is_same<KP::type, KParams>::value, "argument 1 is the KParams");
   constexpr int kPoff = KP::offset();
   __shared__ SharedT<kTailRows> sh;
-#if CMPC_TAIL_PRIO > 0
   __builtin_amdgcn_s_setprio(CMPC_TAIL_PRIO);
-#endif
   const int b = first + (int)blockIdx.x;
   if (b >= *in_count) return;
   const int t = in_list[b];
@@ -1071,9 +1047,7 @@ __global__ __launch_bounds__(64, CMPC_TAIL_WAVES_PER_EU) void cmpc_solve_t_inst_
   using KP = KArg<1, decltype(&cmpc_solve_t_inst_kernel)>;
   static_assert(std::is_same<KP::type, KParams>::value, "argument 1 is the KParams");
   __shared__ SharedT<kTailRows> sh;
-#if CMPC_TAIL_PRIO > 0
   __builtin_amdgcn_s_setprio(CMPC_TAIL_PRIO);
-#endif
   const int b = first + (int)blockIdx.x;
   if (b >= *in_count) return;
   const int t = in_list[b];

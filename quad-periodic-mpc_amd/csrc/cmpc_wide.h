@@ -29,69 +29,22 @@
 #pragma once
 #include "cmpc_common.h"
 
-#ifndef CMPC_DIAG_STOP
-#define CMPC_DIAG_STOP 0
-#endif
 #ifndef CMPC_WIDE_WAVES_PER_EU
 #define CMPC_WIDE_WAVES_PER_EU 3
-#endif
-// hard VGPR cap per row width (0: none); 128 = four waves per SIMD
-// Cholesky and J = L^-T two pivots per step (rank-2 sweeps, half the barriers); 0: one
-#ifndef CMPC_WIDE_CHOL2
-#define CMPC_WIDE_CHOL2 1
-#endif
-#ifndef CMPC_WIDE_J2
-#define CMPC_WIDE_J2 CMPC_WIDE_CHOL2
-#endif
-// wavefronts skip the factorisation steps that cannot change their rows (1); 0: every wave sweeps
-#ifndef CMPC_WIDE_SKIP
-#define CMPC_WIDE_SKIP 1
-#endif
-#ifndef CMPC_WIDE_VGPR_CAP
-#define CMPC_WIDE_VGPR_CAP 0
 #endif
 // one mixed-precision refinement step of the converged active set (wide_refine below); 0: off
 #ifndef CMPC_WIDE_REFINE
 #define CMPC_WIDE_REFINE 1
 #endif
-// refinements per instance at most, and the constraint tolerance (x x_max) after one
-#ifndef CMPC_TRIP_PRIO_AT  // active-set trips after which the N <= 10 builds raise their priority
-#define CMPC_TRIP_PRIO_AT 0
-#endif
-#ifndef CMPC_WIDE_TRIP_PRIO
-#define CMPC_WIDE_TRIP_PRIO 3
-#endif
-// the active set's half-row dot products (z, |d2|^2, J_r . w) as two interleaved FMA chains (A/B)
-#ifndef CMPC_WIDE_DOT2
-#define CMPC_WIDE_DOT2 0
-#endif
-#if CMPC_WIDE_DOT2
-#define W_DOT dot4x2
-#else
-#define W_DOT dot4
-#endif
 #ifndef CMPC_WIDE_PRIO  // s_setprio of the wide classes' waves (0: the default priority)
 #define CMPC_WIDE_PRIO 0
 #endif
-#ifndef CMPC_DIAG_REF_LDSREC
-#define CMPC_DIAG_REF_LDSREC 0
-#endif
-#ifndef CMPC_DIAG_REF_SKIP  // diagnostic builds: skip refinement phases (bit 0..4 = A..E; wrong results)
-#define CMPC_DIAG_REF_SKIP 0
-#endif
-#ifndef CMPC_REF_BFA_MAX  // phases A / D branch-free over the feet / rows up to this width
-#define CMPC_REF_BFA_MAX 96
-#endif
-#ifndef CMPC_REF_BFD_MAX
-#define CMPC_REF_BFD_MAX 96
-#endif
-#ifndef CMPC_REFINE_MAX
-#define CMPC_REFINE_MAX 4
-#endif
-#ifndef CMPC_REFINE_TOL
-#define CMPC_REFINE_TOL 2e-7f
-#endif
-
+// phases A / D of the refinement branch-free over the feet / rows up to this width
+constexpr int CMPC_REF_BFA_MAX = 96;
+constexpr int CMPC_REF_BFD_MAX = 96;
+// refinements per instance at most, and the constraint tolerance (x x_max) after one
+constexpr int CMPC_REFINE_MAX = 4;
+constexpr float CMPC_REFINE_TOL = 2e-7f;
 
 namespace cmpc {
 namespace {
@@ -145,12 +98,8 @@ struct WGeo {
   // R^-1 beside R for the first QI active-set positions (sized to keep each class's workgroups
   // per CU: 80 / 96 six, 120 / 128 four; at 80 the LDS it does not take lets class 1's one-wave
   // workgroups share the CU: QI 56 -> 36 config 3 +1.7 %, profiles/r04_ab/r04_ab80q2)
-#ifdef CMPC_WIDE_QI
-  static constexpr int QI = CMPC_WIDE_QI;
-#else
   static constexpr int QI = (NV == 80) ? 36 : (NV == 96) ? 40 : (NV == 120) ? 48 : (NV == 128) ? 32
                             : (NV == 144) ? 40 : 64;
-#endif
   static constexpr int O_RINV = (GI_END + 3) & ~3;
   static constexpr int PTOT = (mx(mx(PSZ + 12 * 16, PSZ + CH), O_RINV + QI * (QI + 1) / 2) + 3) & ~3;
   // the refinement's fp64 scratch (refine_gradient_seq: 18 + 12 N doubles) in the R^-1 area,
@@ -346,15 +295,10 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
   // of the active-set loop and kept live across every trip. The fp64 scalars come from the kernel
   // arguments (SGPRs) or the LDS, never long-lived VGPRs: the 96-column class has 48 VGPRs beside
   // its J row
-#if CMPC_DIAG_REF_LDSREC  // diagnostic: the phases read LDS garbage in place of the record (timing only)
-  const float* rec = reinterpret_cast<const float*>(&sh.P[0]);
-  (void)rec_in;
-#else
   // global address space: the opaque pointer would otherwise be generic (flat loads, which wait
   // on the LDS counter too)
   const gfloat* rec = (const gfloat*)(rec_in);
   asm volatile("" : "+s"(rec));
-#endif
   double* scr = reinterpret_cast<double*>(&sh.P[G::O_RINV]);
   const int N = P.N;
   const double dt = P.dt64, dth = P.dth64, dt3 = P.dt3_64;
@@ -369,7 +313,7 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
 #endif
   const float* xs = sh.xs();
   // ---- A: per step and axis, sum_b r_b x u_b and sum_b u_b; R, I_w^-1 and the instance scalars
-  if (!(CMPC_DIAG_REF_SKIP & 1)) {
+  {
     const int t = 64 * wave + lane_opq();
     if (t < 3 * N) {
       const int k = t / 3, a = t - 3 * (t / 3);
@@ -454,7 +398,7 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
   }
   wbar();
   // ---- B: d_k,j = (Bdt u_k + Qdt f)_j + (Adt X_d,k-1)_j - X_d,k,j  (X_d,-1 = x0; component 12 = g)
-  if (!(CMPC_DIAG_REF_SKIP & 2)) {
+  {
     const double* R = scr;
     const double* Ii = scr + 9;
     const auto traj = rec + CMPC_REC_HDR;
@@ -514,7 +458,7 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
   wbar();
   // ---- C: wave 0, lane j < 12 owns component j of z, then of mu. Each step's coefficients are
   // re-read from the LDS (R) and the kernel arguments: nothing but z / mu stays live
-  if (wave == 0 && !(CMPC_DIAG_REF_SKIP & 4)) {
+  if (wave == 0) {
     const int j = lane_opq();
     const int jj = (j < 12) ? j : 11;
     const double* R = scr;
@@ -562,7 +506,7 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
   }
   wbar();
   // ---- D: per step, y_k = I_w^-1 nu_k[6:9] and nu_k[9:12] / m into the step's first 6 slots
-  if (!(CMPC_DIAG_REF_SKIP & 8)) {
+  {
     const int t = 64 * wave + lane_opq();
     double ev = 0.0;
     if (t < 6 * N) {
@@ -653,7 +597,7 @@ __device__ __forceinline__ void wide_refine(const float* __restrict__ rec_in, co
   float pa[NC], pb[NC];
 #pragma unroll
   for (int m = 0; m < NC; m++) { pa[m] = 0.f; pb[m] = 0.f; }
-  if (!(CMPC_DIAG_REF_SKIP & 16)) {
+  {
     const int ln = lane_opq();
     static_for<0, NH>([&](auto JC) {
       constexpr int j = decltype(JC)::value;
@@ -701,7 +645,7 @@ __device__ __forceinline__ void wide_refine(const float* __restrict__ rec_in, co
       CMPC_WSWEEP_FENCE(j);
     }
     const float dx = pair_sum(acc.x + acc.y);
-    if (r < n && !(CMPC_DIAG_REF_SKIP & 16)) xv -= dx;
+    if (r < n) xv -= dx;
   }
 }
 
@@ -883,8 +827,6 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
   // published into P's row k (even / odd segments), one s_barrier per step
   int status = g_bad ? (int)CMPC_BAD_INPUT : (int)CMPC_OK;
   float my_inv = 1.f;
-#if CMPC_DIAG_STOP != 3  // diagnostic build 3: stop after the condensation and the H-row load
-#if CMPC_WIDE_CHOL2
   // Two pivots per step (k even, k+1: register k/2 of half 0 and of half 1 of every row), one
   // s_barrier per step instead of per pivot. Each lane publishes its own pivot column entry
   // (half 0: raw column k, half 1: raw column k+1), then every row applies both steps as one
@@ -931,7 +873,7 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
       const float a0 = (r > k && r < NV) ? fmaf(-a1, beta, -hk * (i0 * i0)) : 0.f;
       // a wavefront whose rows are all factored (r <= k) or all padding (r >= n) has a0 = a1 = 0:
       // it skips the sweep (scalar branch; 20 % of the sweep reads at NV = 120, more with more waves)
-      if (CMPC_WIDE_SKIP == 0 || (32 * wave + 31 > k && 32 * wave < n)) {
+      if (32 * wave + 31 > k && 32 * wave < n) {
         const float* prow0 = &sh.P[base + h * st - j0];
         const float* prow1 = &sh.P[base1 + h * st - j0];
 #pragma unroll
@@ -947,39 +889,6 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
       wpin(slot);
     }
   });
-#else
-  static_for<0, NV>([&](auto KC) {
-    constexpr int k = decltype(KC)::value;
-    constexpr int kj = k >> 1, kh = k & 1;
-    constexpr int j0 = G::j0(k);
-    constexpr int base = G::fbase(k);
-    constexpr int st = G::seg(k);
-    if (k < n) {
-      const float mine = slot[kj];
-      const float other = pair_other(mine, h);
-      const float hrk = (h == kh) ? mine : other;          // H[r][k] of the trailing matrix
-      if (h == kh && r >= 2 * j0 && r < NV)
-        sh.P[base + (r & 1) * st + (r >> 1) - j0] = (r >= k) ? mine : 0.f;
-      if (r == k && h == 0) sh.gbuf()[k] = gb;
-      wbar();
-      float d = sh.P[base + kh * st + kj - j0];
-      if (!(d > 0.f)) { status = CMPC_NOT_PD; d = 1e-30f; }
-      const float inv = __builtin_amdgcn_rsqf(d);  // raw v_rsq: d is a normal positive pivot
-      if (r == k) { my_inv = inv; if (h == 0) sh.ibuf()[k] = inv; }
-      const float a = (r > k && r < NV) ? -hrk * (inv * inv) : 0.f;
-      const float* prow = &sh.P[base + h * st - j0];
-#pragma unroll
-      for (int j = j0; j < NH; j += 4) {
-        const float4 r4 = *reinterpret_cast<const float4*>(prow + j);
-        axpy4(a, r4, slot[j + 0], slot[j + 1], slot[j + 2], slot[j + 3]);
-        CMPC_WSWEEP_FENCE(j);
-      }
-      gb = fmaf(a, sh.gbuf()[k], gb);
-      wpin(slot);
-    }
-  });
-#endif
-#endif  // CMPC_DIAG_STOP != 3
   float yv;
   {
     CMPC_WIDE_IDS();
@@ -988,7 +897,6 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
   }
   wbar();
 
-#if CMPC_DIAG_STOP != 1 && CMPC_DIAG_STOP != 3  // diagnostic builds: stop after the Cholesky (1) / after J (2)
   // ---- J = L^-T: row r solves L x = e_r over its half of the columns (LDS reads only; the
   // pivot value x_k lives in the half holding column k: one partner exchange per step)
   {
@@ -1002,7 +910,6 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
       slot[j] = (lr == -2 * j) ? 1.f : 0.f;
     });
   }
-#if CMPC_WIDE_J2
   // two columns per step, as the factorisation (the stored column k+1 is raw: beta corrects it)
   static_for<0, NV / 2>([&](auto KB) {
     constexpr int k = 2 * decltype(KB)::value, k1 = k + 1;
@@ -1012,7 +919,7 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
     constexpr int st = G::seg(k);
     // rows r > k + 1 have x_k = x_k+1 = 0 (L is lower triangular): a wavefront whose rows all lie
     // past the pivot pair skips the step (its slot k stays the +0 the step would store)
-    if (k < n && (CMPC_WIDE_SKIP == 0 || k1 >= 32 * wave)) {
+    if (k < n && k1 >= 32 * wave) {
       wlsync();
       const int h = (lane_opq() >> 5) & 1;
       const float i0 = sh.ibuf()[k], i1 = sh.ibuf()[k1];
@@ -1038,34 +945,6 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
       wpin(slot);
     }
   });
-#else
-  static_for<0, NV>([&](auto KC) {
-    constexpr int k = decltype(KC)::value;
-    constexpr int kj = k >> 1, kh = k & 1;
-    constexpr int j0 = G::j0(k);
-    constexpr int base = G::fbase(k);
-    constexpr int st = G::seg(k);
-    if (k < n) {
-      wlsync();
-      const float inv = sh.ibuf()[k];
-      const float mine = slot[kj];
-      const float other = pair_other(mine, h);
-      const float xk = ((h == kh) ? mine : other) * inv;
-      const float a = -xk * inv;
-      const float* prow = &sh.P[base + h * st - j0];
-#pragma unroll
-      for (int j = j0; j < NH; j += 4) {
-        const float4 r4 = *reinterpret_cast<const float4*>(prow + j);
-        axpy4(a, r4, slot[j + 0], slot[j + 1], slot[j + 2], slot[j + 3]);
-        CMPC_WSWEEP_FENCE(j);
-      }
-      if (h == kh) slot[kj] = xk;
-      wpin(slot);
-    }
-  });
-
-#endif
-#endif
   // ---- unconstrained minimiser x = -J y
   float xv;
   {
@@ -1100,7 +979,7 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
   float up = 0.f;
   int it_refined = -1;  // active-set trips at the last refinement
   int passes = 0;       // refinements so far
-  if (status == CMPC_OK && CMPC_DIAG_STOP == 0) {
+  if (status == CMPC_OK) {
    for (;;) {
     for (;;) {
       wpin(slot);
@@ -1142,9 +1021,6 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
         up = 0.f;
       }
       if (++iters > P.max_iter + 2 * n) { status = CMPC_MAX_ITER; break; }
-#if CMPC_WIDE_PRIO > 0 && CMPC_TRIP_PRIO_AT > 0
-      if (iters == CMPC_TRIP_PRIO_AT) __builtin_amdgcn_s_setprio(CMPC_WIDE_TRIP_PRIO);
-#endif
       // d = J' n+ : rows ia, iz of J through LDS (logical order)
       if (r == cp.ia && cp.ia != cp.iz) {
 #pragma unroll
@@ -1179,8 +1055,8 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
 #pragma unroll
         for (int j = 0; j < NH; j += 4) {
           const float4 m4 = *reinterpret_cast<const float4*>(vb + j);
-          W_DOT(zacc, slot[j + 0], slot[j + 1], slot[j + 2], slot[j + 3], m4);
-          W_DOT(nacc, m4.x, m4.y, m4.z, m4.w, m4);
+          dot4(zacc, slot[j + 0], slot[j + 1], slot[j + 2], slot[j + 3], m4);
+          dot4(nacc, m4.x, m4.y, m4.z, m4.w, m4);
           CMPC_WGI_FENCE(j);
         }
         zv = pair_sum(zacc.x + zacc.y);
@@ -1450,7 +1326,7 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
 #pragma unroll
         for (int j = 0; j < NH; j += 4) {
           const float4 w4 = *reinterpret_cast<const float4*>(vb + j);
-          W_DOT(tacc, slot[j + 0], slot[j + 1], slot[j + 2], slot[j + 3], w4);
+          dot4(tacc, slot[j + 0], slot[j + 1], slot[j + 2], slot[j + 3], w4);
           CMPC_WGI_FENCE(j);
         }
         const float bt = -beta * pair_sum(tacc.x + tacc.y);
@@ -1590,17 +1466,12 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
 #ifndef CMPC_WIDE_BUILD
 #define CMPC_WIDE_BUILD 1
 #endif
-#if CMPC_WIDE_VGPR_CAP > 0
-#define CMPC_WIDE_VGPR_ATTR __attribute__((amdgpu_num_vgpr(CMPC_WIDE_VGPR_CAP)))
-#else
-#define CMPC_WIDE_VGPR_ATTR
-#endif
 
 // REFINE is part of the kernel's name: the refining and plain builds of a class live in different
 // units, and one instantiation name would let the linker keep only one of them
 // (LIT, the literal-model build, is part of the name for the same reason)
 template <int NV, bool PERSIST, bool REFINE, bool LIT = (CMPC_WIDE_LITERAL != 0)>
-__global__ __launch_bounds__(WGeo<NV>::NT, CMPC_WIDE_WAVES_PER_EU) CMPC_WIDE_VGPR_ATTR void cmpc_solve_w_kernel(
+__global__ __launch_bounds__(WGeo<NV>::NT, CMPC_WIDE_WAVES_PER_EU) void cmpc_solve_w_kernel(
     WideArgs A) {
   // kWideMdlOff counts from the head of the argument segment: WideArgs is argument 0
   using KA = KArg<0, decltype(&cmpc_solve_w_kernel<NV, PERSIST, REFINE, LIT>)>;
@@ -1640,7 +1511,7 @@ __global__ __launch_bounds__(WGeo<NV>::NT, CMPC_WIDE_WAVES_PER_EU) CMPC_WIDE_VGP
 // which a handle with a table never launches (the host clears KParams::mdl_default).
 #if !CMPC_WIDE_LITERAL
 template <int NV, bool PERSIST, bool REFINE>
-__global__ __launch_bounds__(WGeo<NV>::NT, CMPC_WIDE_WAVES_PER_EU) CMPC_WIDE_VGPR_ATTR void cmpc_solve_w_inst_kernel(
+__global__ __launch_bounds__(WGeo<NV>::NT, CMPC_WIDE_WAVES_PER_EU) void cmpc_solve_w_inst_kernel(
     WideArgs A) {
   __shared__ SharedW<NV> sh;
 #if CMPC_WIDE_PRIO > 0

@@ -2,18 +2,10 @@
 // N = 20, n = 120; the 128-column build keeps n 121-128) (kernel template: cmpc_wide.h).
 // four waves per SIMD: 118 VGPRs and 34 KB of LDS (the stage buffers share P's tail), four
 // four-wave workgroups per CU
-#ifndef CMPC_WIDE_WAVES_PER_EU
 #define CMPC_WIDE_WAVES_PER_EU 4
-#endif
-#ifndef CMPC_WIDE_BUILD
 #define CMPC_WIDE_BUILD 1  // one workgroup per entry here; the persistent form in cmpc_wide_w120p.hip
-#endif
-#ifndef CMPC_WIDE_REFINE
 #define CMPC_WIDE_REFINE 0  // N <= 10 (no refinement); the refining builds: cmpc_wide_w120r.hip, w120pr.hip
-#endif
-#ifndef CMPC_WIDE_PRIO
 #define CMPC_WIDE_PRIO 1  // N <= 10: issue priority over the class-1 waves (config 2 +1.9 %, config 3 +0.2 %, r04_p)
-#endif
 #include "cmpc_wide.h"
 
 namespace cmpc {

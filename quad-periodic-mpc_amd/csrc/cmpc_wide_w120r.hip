@@ -1,8 +1,6 @@
 // cmpc_wide_w120r.hip — the 120-column wide class with the fp64 refinement step of the converged
 // active set (cmpc_wide.h wide_refine; horizons N > 10), one workgroup per list entry.
-#ifndef CMPC_WIDE_WAVES_PER_EU
 #define CMPC_WIDE_WAVES_PER_EU 4
-#endif
 #define CMPC_WIDE_BUILD 1
 #define CMPC_WIDE_REFINE 1
 #include "cmpc_wide.h"

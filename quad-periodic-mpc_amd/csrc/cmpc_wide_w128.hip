@@ -1,12 +1,8 @@
 // cmpc_wide_w128.hip — wide size class with 128-column rows (kernel template: cmpc_wide.h).
 // four waves per SIMD: 124 VGPRs and 38 KB of LDS (the stage buffers share P's tail), four
 // four-wave workgroups per CU
-#ifndef CMPC_WIDE_WAVES_PER_EU
 #define CMPC_WIDE_WAVES_PER_EU 4
-#endif
-#ifndef CMPC_WIDE_BUILD
 #define CMPC_WIDE_BUILD 1  // one workgroup per entry here; the persistent form in cmpc_wide_w128p.hip
-#endif
 #include "cmpc_wide.h"
 
 namespace cmpc {

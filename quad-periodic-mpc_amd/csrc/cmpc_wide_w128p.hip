@@ -1,8 +1,6 @@
 // cmpc_wide_w128p.hip — the persistent launch form of the 128-column wide class (kernel template:
 // cmpc_wide.h; launch_solve uses it when the class does not hold the trot size n = 6N).
-#ifndef CMPC_WIDE_WAVES_PER_EU
 #define CMPC_WIDE_WAVES_PER_EU 4
-#endif
 #define CMPC_WIDE_BUILD 2
 #include "cmpc_wide.h"
 

@@ -1,18 +1,10 @@
 // cmpc_wide_w80.hip — wide size class with 80-column rows (kernel template: cmpc_wide.h).
 // five waves per SIMD (94 VGPRs, no spills): config 3's n 65-80 instances finish inside class 1's
 // run
-#ifndef CMPC_WIDE_WAVES_PER_EU
 #define CMPC_WIDE_WAVES_PER_EU 5
-#endif
-#ifndef CMPC_WIDE_BUILD
 #define CMPC_WIDE_BUILD 1  // one workgroup per entry here; the persistent form in cmpc_wide_w80p.hip
-#endif
-#ifndef CMPC_WIDE_REFINE
 #define CMPC_WIDE_REFINE 0  // N <= 10 (no refinement); the refining builds: cmpc_wide_w80r.hip, w80pr.hip
-#endif
-#ifndef CMPC_WIDE_PRIO
 #define CMPC_WIDE_PRIO 1  // N <= 10: issue priority over the class-1 waves (config 2 +1.9 %, config 3 +0.2 %, r04_p)
-#endif
 #include "cmpc_wide.h"
 
 namespace cmpc {

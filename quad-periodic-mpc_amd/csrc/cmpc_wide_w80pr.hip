@@ -1,8 +1,6 @@
 // cmpc_wide_w80pr.hip — the persistent launch form of the 80-column wide class with the fp64
 // refinement step (cmpc_wide.h wide_refine; horizons N > 10).
-#ifndef CMPC_WIDE_WAVES_PER_EU
 #define CMPC_WIDE_WAVES_PER_EU 5
-#endif
 #define CMPC_WIDE_BUILD 2
 #define CMPC_WIDE_REFINE 1
 #include "cmpc_wide.h"

@@ -1,15 +1,9 @@
 // cmpc_wide_w96p.hip — the persistent launch form of the 96-column wide class (kernel template:
 // cmpc_wide.h; launch_solve uses it when the class does not hold the trot size n = 6N).
-#ifndef CMPC_WIDE_WAVES_PER_EU
 #define CMPC_WIDE_WAVES_PER_EU 5
-#endif
 #define CMPC_WIDE_BUILD 2
-#ifndef CMPC_WIDE_REFINE
 #define CMPC_WIDE_REFINE 0  // N <= 10; the refining persistent build: cmpc_wide_w96pr.hip
-#endif
-#ifndef CMPC_WIDE_PRIO
 #define CMPC_WIDE_PRIO 1  // N <= 10: issue priority over the class-1 waves (config 2 +1.9 %, config 3 +0.2 %, r04_p)
-#endif
 #include "cmpc_wide.h"
 
 namespace cmpc {

@@ -1,9 +1,7 @@
 // cmpc_wide_w96rd.hip — the default robot's build (the model as literals, CMPC_WIDE_LITERAL) of
 // the 96-column wide class with the fp64 refinement step of the converged
 // active set (cmpc_wide.h wide_refine; horizons N > 10), one workgroup per list entry.
-#ifndef CMPC_WIDE_WAVES_PER_EU
 #define CMPC_WIDE_WAVES_PER_EU 5
-#endif
 #define CMPC_WIDE_BUILD 1
 #define CMPC_WIDE_REFINE 1
 #define CMPC_WIDE_LITERAL 1

@@ -1,6 +1,6 @@
 // cmpc_mfma_probe — the register layout and rounding of v_mfma_f32_4x4x1_16b_f32 with the
 // A-operand broadcast (cbsz 4, abid b), as the class-1 row sweeps use it (cmpc_class1.hip,
-// CMPC_C1_MFMA): one wavefront, for every abid 0..15
+// mfma_chunk): one wavefront, for every abid 0..15
 //   D(lane v, register i) = A(lane 4 abid + i) * B(lane v) + C(lane v, register i)
 // is compared in every lane and register with the host's fmaf. Two input sets: normal values
 // with zeros and negatives mixed in, and one whose inputs, addends or products are denormal.

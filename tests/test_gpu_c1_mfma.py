@@ -1,4 +1,4 @@
-"""Class 1's row sweeps as broadcast MFMA outer products (cmpc_class1.hip, CMPC_C1_MFMA).
+"""Class 1's row sweeps as broadcast MFMA outer products (cmpc_class1.hip, mfma_chunk).
 
 The Cholesky's trailing sweep and the active set's reflection update take the broadcast column
 from lane c's register through v_mfma_f32_4x4x1_16b_f32 (cbsz 4, abid = c / 4) instead of from an

@@ -1,5 +1,5 @@
-"""Class 1's two-stance rows (cmpc_class1.hip, CMPC_C1_STATIC2): a table with exactly two stance feet
-at every step (and 6 N <= the build's row width) is condensed straight into the row registers, lane
+"""Class 1's two-stance rows (cmpc_class1.hip, the st2 path of solve_c1): a table with exactly two
+stance feet at every step (and 6 N <= the build's row width) is condensed straight into the row registers, lane
 v computing its whole row, the entries below the diagonal from its own recursion continued below its
 step. Every other table takes the exchange through the LDS.
 

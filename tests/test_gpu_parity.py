@@ -38,7 +38,7 @@ def tol_for(N):
 
 
 ORDER_MIN_N = 11         # below this every instance is held to 1e-4 against the default-order
-                         # reference (the refinement's first horizon, CMPC_REFINE_FROM_N)
+                         # reference (the first horizon at which the wide classes refine)
 FP64_TOL = 1e-5          # ours against the fp64 optimum on those instances (measured <= 4e-6)
 
 

@@ -16,7 +16,7 @@ handles for the single-instance fast path and the reference ABI.
 
 Kernel safety with non-finite input, from the code: every loop of classify, class 1, the tail class
 and the wide classes is bounded by integers (the active set by max_iter + 2n trips, the refinement
-by CMPC_REFINE_MAX passes, the lists by their counts), and no address, lane index or trip count is
+by its constant cap of passes, the lists by their counts), and no address, lane index or trip count is
 computed from a float (a NaN only ever loses a comparison: `sl < best`, `r > 0`, `zn > 1e-9 dn`,
 `d > 0` all take their "no" side)."""
 import ctypes
