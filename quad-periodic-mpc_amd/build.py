@@ -17,14 +17,35 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libcmpc_hip.so")
 OBJ = os.path.join(ROOT, "build", "obj")
-# one translation unit per kernel family so the large unrolled kernels compile in parallel
-SOURCES = ["cmpc_tail.hip", "cmpc_wide_w256.hip", "cmpc_wide_w192.hip", "cmpc_class1.hip", "cmpc_wide_w80.hip", "cmpc_wide_w96.hip",
-           "cmpc_wide_w120.hip", "cmpc_wide_w128.hip", "cmpc_wide_w144.hip", "cmpc_wide_w80p.hip",
-           "cmpc_wide_w96p.hip", "cmpc_wide_w120p.hip", "cmpc_wide_w128p.hip", "cmpc_wide_w80r.hip",
-           "cmpc_wide_w96r.hip", "cmpc_wide_w120r.hip", "cmpc_wide_w80pr.hip", "cmpc_wide_w96pr.hip",
-           "cmpc_wide_w120pr.hip", "cmpc_wide_w96prd.hip", "cmpc_wide_w120prd.hip", "cmpc_wide_w96rd.hip", "cmpc_wide_w120rd.hip", "cmpc_condense.hip", "cmpc_launch.hip", "cmpc_inst_table.hip", "cmpc_estimator.hip", "cmpc_assemble.hip",
-           "cmpc_admm.hip", "cmpc_quadprog.hip", "cmpc_evaluate.hip", "cmpc_condense_inst.hip",
-           "cmpc_evaluate_inst.hip", "cmpc_abi.cpp"]
+
+
+def wide_builds() -> list:
+    """The rows (NV, PERSIST, REFINE, LIT) of kWideBuild in csrc/cmpc_wide_builds.h, the one statement of
+    which builds of the wide kernel template exist."""
+    text = open(os.path.join(CSRC, "cmpc_wide_builds.h")).read()
+    body = re.search(r"kWideBuild\[\]\s*=\s*\{(.*?)\n\};", text, re.S).group(1)
+    body = re.sub(r"//[^\n]*", "", body)
+    rows = [tuple(map(int, r)) for r in re.findall(r"\{(\d+),\s*([01]),\s*([01]),\s*([01])\}", body)]
+    if not rows or len(set(rows)) != len(rows):
+        raise RuntimeError("cmpc_wide_builds.h: no rows, or a row twice, in kWideBuild")
+    return rows
+
+
+def wide_unit(row: tuple) -> tuple:
+    return ("cmpc_wide_unit.hip", ("CMPC_UNIT_WIDE=%d,%d,%d,%d" % row,))
+
+
+# The translation units as (source, defines): one unit per kernel family, and one per build of the
+# wide template (compiled side by side the kernels spilled), so the large unrolled kernels compile
+# in parallel. The widest first: they take longest.
+UNITS = ([("cmpc_tail.hip", ()), ("cmpc_class1.hip", ())] +
+         [wide_unit(r) for r in sorted(wide_builds(), key=lambda r: -r[0])] +
+         [("cmpc_condense.hip", ()), ("cmpc_launch.hip", ()), ("cmpc_inst_table.hip", ()),
+          ("cmpc_estimator.hip", ()), ("cmpc_assemble.hip", ()), ("cmpc_admm.hip", ()), ("cmpc_quadprog.hip", ()),
+          ("cmpc_evaluate.hip", ()),
+          # the per-instance builds of the two hooks, each kernel in a unit of its own
+          ("cmpc_condense.hip", ("CMPC_CONDENSE_INST=1",)), ("cmpc_evaluate.hip", ("CMPC_EVALUATE_INST=1",)),
+          ("cmpc_abi.cpp", ())])
 ARCH = os.environ.get("CMPC_OFFLOAD_ARCH", "gfx950")
 # -fno-slp-vectorize: the SLP pass packs adjacent row updates into v_pk_fma_f32, which ties
 # slot registers into 64-bit pairs and made the register-resident rows spill (DESIGN.md §4.1)
@@ -66,13 +87,14 @@ def build(force: bool = False, verbose: bool = False, out: str | None = None,
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     os.makedirs(OBJ, exist_ok=True)
 
-    def compile_one(src: str) -> str:
+    def compile_one(unit: tuple) -> str:
+        src, unit_defines = unit
         path = os.path.join(CSRC, src)
-        obj = _obj(src, defines)
+        obj = _obj(src, unit_defines + tuple(defines))
         if not force and not _stale(obj, _deps(path)):
             return obj
-        cmd = [hipcc, f"--offload-arch={ARCH}", *FLAGS, *[f"-D{d}" for d in defines], "-c", path,
-               "-o", obj + ".tmp"]
+        cmd = [hipcc, f"--offload-arch={ARCH}", *FLAGS, *[f"-D{d}" for d in unit_defines + tuple(defines)], "-c",
+               path, "-o", obj + ".tmp"]
         if src.endswith(".cpp"):
             cmd[1:1] = ["-x", "hip"]
         if verbose:
@@ -81,9 +103,9 @@ def build(force: bool = False, verbose: bool = False, out: str | None = None,
         os.replace(obj + ".tmp", obj)
         return obj
 
-    jobs = max(1, min(len(SOURCES), int(os.environ.get("MAX_JOBS", os.cpu_count() or 1))))
+    jobs = max(1, min(len(UNITS), int(os.environ.get("MAX_JOBS", os.cpu_count() or 1))))
     with ThreadPoolExecutor(jobs) as ex:
-        objs = list(ex.map(compile_one, SOURCES))
+        objs = list(ex.map(compile_one, UNITS))
     if not force and not _stale(lib, objs):
         return lib
     tmp = lib + ".tmp"
@@ -148,7 +170,7 @@ def build_plan_dump() -> str:
     host compiler alone, which keeps that header free of HIP; tests/test_launch_plan.py runs it."""
     exe = os.path.join(PKG, "cmpc_plan_dump")
     src = os.path.join(CSRC, "tools", "cmpc_plan_dump.cpp")
-    if _stale(exe, [src, os.path.join(CSRC, "cmpc_plan.h")]):
+    if _stale(exe, _deps(src)):
         subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-o", exe + ".tmp", src], check=True)
         os.replace(exe + ".tmp", exe)
     return exe

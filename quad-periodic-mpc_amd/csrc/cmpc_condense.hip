@@ -8,7 +8,7 @@
 // z_i = Adt' z_{i+1}, the source term masked off) and writes its own entries on both sides of the
 // diagonal, nothing mirrored: what class 1's two-stance rows compute (cmpc_class1.hip,
 // the st2 path of solve_c1), here under the fp64 check of the parity hook.
-// CMPC_CONDENSE_INST = 1 (cmpc_condense_inst.hip, which includes this file): the per-instance build
+// CMPC_CONDENSE_INST = 1 (this file's second unit in build.py's UNITS): the per-instance build
 // for a handle with a table (cmpc_batch_set_instance_params), a kernel and a launcher of their own
 // names in a unit of their own, so that this unit compiles the shared kernel exactly as before.
 #ifndef CMPC_CONDENSE_INST
@@ -137,7 +137,7 @@ hipError_t launch_condense_inst(const float* d_recs, int batch, const KParams& P
 }
 #else
 hipError_t launch_condense_inst(const float* d_recs, int batch, const KParams& P, float* d_H, float* d_g,
-                                bool rows, hipStream_t stream);  // cmpc_condense_inst.hip
+                                bool rows, hipStream_t stream);  // this file's CMPC_CONDENSE_INST unit
 
 hipError_t launch_condense(const float* d_recs, int batch, const KParams& P, float* d_H, float* d_g,
                            bool rows, hipStream_t stream) {

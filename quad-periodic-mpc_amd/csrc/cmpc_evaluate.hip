@@ -20,7 +20,7 @@
 //      its gap / slack / swing terms
 //   F  xor-butterfly reductions over the wave: the same order for every instance, whatever the batch
 #ifndef CMPC_EVALUATE_INST
-#define CMPC_EVALUATE_INST 0  // 1: the per-instance build (cmpc_evaluate_inst.hip; see the kernel below)
+#define CMPC_EVALUATE_INST 0  // 1: the per-instance build (a second unit of this file; see the kernel below)
 #endif
 #include "cmpc_common.h"
 
@@ -69,7 +69,7 @@ __device__ __forceinline__ double bfly_max(double v) {
   return v;
 }
 
-// CMPC_EVALUATE_INST = 1 (cmpc_evaluate_inst.hip, which includes this file): the per-instance build
+// CMPC_EVALUATE_INST = 1 (this file's second unit in build.py's UNITS): the per-instance build
 // for a handle with a table (cmpc_batch_set_instance_params, _set_instance_costs), a kernel and a launcher of their own
 // names in a unit of their own, so that this unit compiles the shared kernel exactly as before. The
 // kernel's body is the one below: instance i first takes its inertia doubles from row i of the
@@ -377,7 +377,7 @@ hipError_t launch_evaluate_inst(const float* d_recs, const float* d_forces, int 
 #else
 hipError_t launch_evaluate_inst(const float* d_recs, const float* d_forces, int batch, const KParams& P,
                                 double alpha, const double* inst_rows, float* d_xpred, double* d_cert,
-                                hipStream_t stream);  // cmpc_evaluate_inst.hip
+                                hipStream_t stream);  // this file's CMPC_EVALUATE_INST unit
 
 hipError_t launch_evaluate(const float* d_recs, const float* d_forces, int batch, const KParams& P,
                            double alpha, const double* ib64, float* d_xpred, double* d_cert,

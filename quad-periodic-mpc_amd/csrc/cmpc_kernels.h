@@ -129,28 +129,28 @@ hipError_t launch_solve(const float* d_recs, int batch, const KParams& P, float*
                         uint8_t* d_status, int32_t* d_iters, int* d_work, int max_batch,
                         hipStream_t stream, LaunchCtx& ctx, hipEvent_t* ev = nullptr,
                         const uint8_t* d_due = nullptr);
-// per-class launchers (cmpc_class1.hip, cmpc_wide_w*.hip)
+// per-class launchers (cmpc_class1.hip; the wide classes' below)
 hipError_t launch_class1(int nv, const float* d_recs, int batch, const KParams& P, float* d_forces,
                          uint8_t* d_status, int32_t* d_iters, const int* in_list, const int* in_count,
                          int* ovf_list, int* ovf_count, int grid, hipStream_t stream);
-// wide classes, two lanes per row, NV/32 wavefronts (cmpc_wide_w{80,96,120,128,144,192,256}.hip)
-#define CMPC_DECL_WIDE(W)                                                                          \
-  hipError_t launch_wide_w##W(const float* d_recs, const KParams& P, float* d_forces,             \
-                              uint8_t* d_status, int32_t* d_iters, const int* in_list,            \
-                              const int* in_count, int* deq, int grid, hipStream_t stream,     \
-                              int base = 0);
-CMPC_DECL_WIDE(80)
-CMPC_DECL_WIDE(96)
-CMPC_DECL_WIDE(120)
-CMPC_DECL_WIDE(128)
-CMPC_DECL_WIDE(80_persist)
-CMPC_DECL_WIDE(96_persist)
-CMPC_DECL_WIDE(120_persist)
-CMPC_DECL_WIDE(128_persist)
-CMPC_DECL_WIDE(144)
-CMPC_DECL_WIDE(192)
-CMPC_DECL_WIDE(256)
-#undef CMPC_DECL_WIDE
+// One launch of a wide class (two lanes per row, NV/32 wavefronts) over a classify list.
+struct WideCall {
+  const float* recs;
+  float* forces;
+  uint8_t* status;
+  int32_t* iters;
+  const int* list;   // the class's instance list and its length (on the device)
+  const int* count;
+  int* deq;          // the persistent workgroups' dequeue counter; nullptr: workgroup i takes entry i, once
+  int grid;
+  hipStream_t stream;
+  int base;          // persistent form: first list entry it takes (0, or the grid of a one-per-entry launch)
+};
+// The launcher of one build of the wide kernel template: defined in cmpc_wide.h and instantiated
+// once per row of kWideBuild (cmpc_wide_builds.h), each in a unit of its own (cmpc_wide_unit.hip).
+// Only launch_wide (cmpc_launch.hip) names them, through the table.
+template <int NV, bool PERSIST, bool REFINE, bool LIT>
+hipError_t launch_wide_build(const KParams& P, const WideCall& c);
 // the tail class (cmpc_tail.hip): 8 tail rows beside class 1's 64 (n <= 72), one wavefront per
 // instance over its list, one workgroup per possible entry; an instance whose active set outgrows
 // 64 positions is appended to ovf_list (batched) or, with ovf_list == nullptr, gets status

@@ -5,13 +5,16 @@
 //     instances with n > 64 appended to the list of their class;
 //   class 1 (cmpc_class1.hip): every instance, one wavefront each; exits when n > 64;
 //   wide classes (cmpc_wide.h: two lanes per row, NV/32 wavefronts; NV = 80, 96, 120, 128, 144,
-//     192, 256; n <= 12 N <= 240 at CMPC_MAX_HORIZON = 20) each over its own list, on two side
+//     192, 256; n <= 12 N <= 240 at CMPC_MAX_HORIZON = 20; their builds: the table of
+//     cmpc_wide_builds.h, chosen by launch_wide below) each over its own list, on two side
 //     streams forked after classify, so they run concurrently with class 1 and with each
 //     other. At N = 10 they are a latency-bound tail (few, long solves); at N = 16..20 the 128-
 //     and 192-column classes carry the batch and run side by side on the two streams.
 //   due form (cmpc_batch_solve_due): the classify pass lists only the due instances and every
 //     class, class 1 included, runs over its list.
 #include <stdlib.h>
+
+#include <utility>
 
 #include "cmpc_kernels.h"
 
@@ -140,16 +143,22 @@ const PlanKnobs& plan_knobs() {
   return k;
 }
 
-// the launchers of the wide classes kW80 .. kW256: deq == nullptr one workgroup per entry (the
-// classes with both builds), else persistent workgroups; and the persistent build of each class
-// with a null dequeue counter (its loop runs once per workgroup)
-using WideFn = hipError_t (*)(const float*, const KParams&, float*, uint8_t*, int32_t*, const int*, const int*,
-                              int*, int, hipStream_t, int);
-constexpr WideFn kWideFn[] = {launch_wide_w80,  launch_wide_w96,  launch_wide_w120, launch_wide_w128,
-                              launch_wide_w144, launch_wide_w192, launch_wide_w256};
-constexpr WideFn kWidePersistFn[] = {launch_wide_w80_persist,  launch_wide_w96_persist, launch_wide_w120_persist,
-                                     launch_wide_w128_persist, launch_wide_w144,        launch_wide_w192,
-                                     launch_wide_w256};
+// One launch of wide class cls (kW80 .. kW256) in the launch form wanted: the build that
+// select_wide_build (cmpc_wide_builds.h) picks for the form, P.refine and P.mdl_default, through a
+// table of the launchers of kWideBuild's rows in row order. A class without a one-per-entry build
+// gets its persistent one; with c.deq == nullptr that runs its loop once per workgroup.
+template <size_t... I>
+hipError_t launch_wide_row(int row, const KParams& P, const WideCall& c, std::index_sequence<I...>) {
+  using Fn = hipError_t (*)(const KParams&, const WideCall&);
+  static constexpr Fn kFn[] = {&launch_wide_build<kWideBuild[I].nv, kWideBuild[I].persistent, kWideBuild[I].refine,
+                                                  kWideBuild[I].literal>...};
+  return kFn[row](P, c);
+}
+hipError_t launch_wide(int cls, bool persistent, const KParams& P, const WideCall& c) {
+  const int row = select_wide_build(kClass[cls].width, persistent, P.refine != 0, P.mdl_default != 0);
+  if (row < 0) return hipErrorInvalidValue;
+  return launch_wide_row(row, P, c, std::make_index_sequence<kNumWideBuilds>());
+}
 
 }  // namespace
 
@@ -211,18 +220,20 @@ hipError_t launch_solve(const float* d_recs, int batch, const KParams& P, float*
     const hipError_t r = launch_tail(d_recs, P, d_forces, d_status, d_iters, list[lt], &cnt[1 + lt], list[lh],
                                      &cnt[1 + lh], plan.tail_grid, s, plan.tail_rest);
     if (r != hipSuccess) return r;
-    return launch_wide_w80(d_recs, P, d_forces, d_status, d_iters, list[lh], &cnt[1 + lh], &cnt[kDeq + lh],
-                           kHandoffGrid, s);
+    return launch_wide(kW80, true, P,
+                       {d_recs, d_forces, d_status, d_iters, list[lh], &cnt[1 + lh], &cnt[kDeq + lh], kHandoffGrid, s, 0});
   };
   auto wide = [&](const WideLaunch& w) -> hipError_t {
     const int l = kClass[w.cls].list;
-    const WideFn fn = kWideFn[w.cls - kW80];
     hipStream_t s = ctx.side[w.side];
-    const hipError_t r = fn(d_recs, P, d_forces, d_status, d_iters, list[l], &cnt[1 + l],
-                            w.persistent ? &cnt[kDeq + l] : nullptr, w.grid, s, 0);
+    const hipError_t r = launch_wide(w.cls, w.persistent, P,
+                                     {d_recs, d_forces, d_status, d_iters, list[l], &cnt[1 + l],
+                                      w.persistent ? &cnt[kDeq + l] : nullptr, w.grid, s, 0});
     if (r != hipSuccess || w.rest_grid == 0) return r;
-    return fn(d_recs, P, d_forces, d_status, d_iters, list[l], &cnt[1 + l], &cnt[kDeq + l], w.rest_grid, s,
-              w.rest_base);
+    // the looping launch behind a one-per-entry launch of a predicted grid: the entries from rest_base on
+    return launch_wide(w.cls, true, P,
+                       {d_recs, d_forces, d_status, d_iters, list[l], &cnt[1 + l], &cnt[kDeq + l], w.rest_grid, s,
+                        w.rest_base});
   };
 
   if (plan.nsides == 0 && plan.classify != kClassifyNone) {
@@ -293,16 +304,16 @@ hipError_t launch_single(const float* d_rec, int n, const KParams& P, float* d_f
   const bool in_tail = knobs.tail != 0 && tail_class(P.refine != 0, P.N, n);
   if (allow_tail && in_tail)
     return launch_tail(d_rec, P, d_forces, d_status, d_iters, lst, cnt, nullptr, nullptr, 1, stream);
+  const WideCall one{d_rec, d_forces, d_status, d_iters, lst, cnt, nullptr, 1, stream, 0};
   if (!allow_tail && in_tail)  // a tail-class hand-off: the form the batched launch uses
-    return launch_wide_w80_persist(d_rec, P, d_forces, d_status, d_iters, lst, cnt, nullptr, 1, stream);
+    return launch_wide(kW80, true, P, one);
   // the launch form the batched launch of this class would pick for a batch of one (one workgroup
   // per entry; the persistent form runs its loop once with deq == nullptr). Both forms round
   // alike (-ffp-contract=on, build.py): tests/test_gpu_parity.py::test_batch_size_invariance
   // solves the same records in a batch of 16384 (persistent sparse classes), in batches of 4096
   // and one at a time and requires bitwise-equal forces
   const int c = wide_class(n);
-  const WideFn fn = one_per_entry(kClass[c], P.N, 1, knobs) ? kWideFn[c - kW80] : kWidePersistFn[c - kW80];
-  return fn(d_rec, P, d_forces, d_status, d_iters, lst, cnt, nullptr, 1, stream, 0);
+  return launch_wide(c, !one_per_entry(kClass[c], P.N, 1, knobs), P, one);
 }
 
 }  // namespace cmpc

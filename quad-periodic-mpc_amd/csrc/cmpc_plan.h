@@ -6,6 +6,8 @@
 #pragma once
 #include <math.h>
 
+#include "cmpc_wide_builds.h"
+
 #if defined(__HIPCC__)
 #define CMPC_HD __host__ __device__
 #else
@@ -110,7 +112,7 @@ struct PlanKnobs {
   int sparse_side = 1;      // CMPC_SPARSE_SIDE: the sides of the 144 / 192 classes as two digits
 };
 
-// Launch form of a wide class with both builds (cmpc_wide.h): one workgroup per list entry for the
+// Launch form of a wide class with both builds (cmpc_wide_builds.h): one workgroup per list entry for the
 // populous classes, persistent workgroups for the sparse ones. Populous: the class meets
 // 6N +- 3 sqrt(N), the trot size (two feet in stance at every step) +- one standard deviation of n
 // = 3 Bin(4N, 1/2) under random contact tables. Measured (profiles/r03_ab/r03_e): every class
@@ -248,7 +250,8 @@ inline SolvePlan plan_solve(int N, bool refine, int batch, bool due, const int* 
     WideLaunch& w = p.wide[p.nwide++];
     w.cls = c;
     w.side = side_of[c - kW80];
-    w.persistent = c >= kW144 || !one_per_entry(kClass[c], N, batch, k);  // from 144 columns: one build
+    // (a class built persistent only is launched persistent whatever its population)
+    w.persistent = !wide_has_form(kClass[c].width, false) || !one_per_entry(kClass[c], N, batch, k);
     w.grid = grid_of(kClass[c].list);
     const bool rest = !w.persistent && hinting && w.grid < batch;
     w.rest_grid = rest ? kRestGrid : 0;

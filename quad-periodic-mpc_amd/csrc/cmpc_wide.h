@@ -26,19 +26,14 @@
 //   * the QP's triangular factor R is explicit, packed by columns in LDS, maintained by
 //     wavefront 0 with readlane chains (RQ = NV/64 active-set positions per lane).
 // Everything is fp32 (the reference condenses in fp32: common_types.h:14).
+//
+// Builds (cmpc_wide_builds.h): the template is compiled once per row (NV, PERSIST, REFINE, LIT) of
+// kWideBuild, each row in a translation unit of its own (cmpc_wide_unit.hip), as
+// launch_wide_build<NV, PERSIST, REFINE, LIT> at the end of this file. Waves per SIMD and the
+// issue priority follow from the row (wide_waves, wide_prio).
 #pragma once
 #include "cmpc_common.h"
 
-#ifndef CMPC_WIDE_WAVES_PER_EU
-#define CMPC_WIDE_WAVES_PER_EU 3
-#endif
-// one mixed-precision refinement step of the converged active set (wide_refine below); 0: off
-#ifndef CMPC_WIDE_REFINE
-#define CMPC_WIDE_REFINE 1
-#endif
-#ifndef CMPC_WIDE_PRIO  // s_setprio of the wide classes' waves (0: the default priority)
-#define CMPC_WIDE_PRIO 0
-#endif
 // phases A / D of the refinement branch-free over the feet / rows up to this width
 constexpr int CMPC_REF_BFA_MAX = 96;
 constexpr int CMPC_REF_BFD_MAX = 96;
@@ -236,22 +231,18 @@ struct WideArgs {
 // byte offset of the kernel's KModel in its argument segment (WideArgs is the one argument): the
 // model's values are read there where they are used (karg_late), not held from kernel entry
 constexpr int kWideMdlOff = (int)(offsetof(WideArgs, P) + offsetof(KParams, mdl));
-// CMPC_WIDE_LITERAL = 1: the build of the default robot (m = 12, I_body = diag(.07, .26, .242),
-// RobotState.h:25-26) with the model as literals, as before the model was a parameter; the launcher
-// picks it when the handle's model is the default (KParams::mdl_default), so the default pays nothing
-// for the parameter. Built for the refining 96- and 120-column classes in both launch forms (N = 16
-// and N = 20 trot, the measured workloads); the model-reading build is the unit without the "d".
-#ifndef CMPC_WIDE_LITERAL
-#define CMPC_WIDE_LITERAL 0
-#endif
+// LIT (WideBuild::literal): the build of the default robot (m = 12, I_body = diag(.07, .26, .242),
+// RobotState.h:25-26) with the model as literals, as before the model was a parameter; the selector
+// (select_wide_build) picks it when the handle's model is the default (KParams::mdl_default), so the
+// default pays nothing for the parameter.
 // 1 / m in phases B and D of the refinement: the grouped load's value, held across the phases. The
 // 256-column build alone re-reads it at each use: at its 256-VGPR cap, holding it cost 20 B of
 // scratch per lane
 // (INST, the per-instance build: the same re-read from the instance's table entry ie)
-template <int NV, bool INST = false>
-__device__ __forceinline__ double ref_im64(double grouped, const KInst* ie = nullptr) {
+template <int NV, bool LIT, bool INST>
+__device__ __forceinline__ double ref_im64(double grouped, const KInst* ie) {
   if constexpr (NV > 192 && INST) return inst_late<double>(ie, kInstIm64Off);
-  else if constexpr (NV > 192 && !CMPC_WIDE_LITERAL) return karg_late<double>(kWideMdlOff + (int)offsetof(KModel, im64));
+  else if constexpr (NV > 192 && !LIT) return karg_late<double>(kWideMdlOff + (int)offsetof(KModel, im64));
   else return grouped;
 }
 
@@ -286,9 +277,9 @@ __device__ __forceinline__ double ref_im64(double grouped, const KInst* ie = nul
 // scratch (24 + 12 N doubles in the R^-1 area). (Out of line, the call saved 95 VGPRs of the J
 // rows around it: N = 16 10.0 -> 8.8 M QP/s, abr2.)
 // INST (the per-instance build): the model's fp64 values come from the instance's table entry ie.
-template <int NV, bool INST = false>
+template <int NV, bool LIT, bool INST>
 __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in, const KParams& P,
-                                                     SharedW<NV>& sh, int wave, const KInst* ie = nullptr) {
+                                                SharedW<NV>& sh, int wave, const KInst* ie) {
   using G = WGeo<NV>;
   constexpr int S0 = 24;  // [0..8] R, [9..17] I_w^-1, [18] x_drag, [19] f_est term, [20] x0[12], [21..23] rpy
   // an opaque record pointer keeps its loads (and the arithmetic on them) from being hoisted out
@@ -303,14 +294,10 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
   const int N = P.N;
   const double dt = P.dt64, dth = P.dth64, dt3 = P.dt3_64;
   // the model's fp64 values: one grouped scalar load here, at the head of the refinement
-#if CMPC_WIDE_LITERAL
-  const double ii0 = 1.0 / 0.07, ii1 = 1.0 / 0.26, ii2 = 1.0 / 0.242, im64 = 1.0 / 12.0;
-#else
-  kf64x4 m64;
+  kf64x4 m64 = {1.0 / 0.07, 1.0 / 0.26, 1.0 / 0.242, 1.0 / 12.0};  // (LIT: the default robot's)
   if constexpr (INST) m64 = inst_late<kf64x4>(ie, kInstIinv64Off);
-  else m64 = karg_late<kf64x4>(kWideMdlOff + (int)offsetof(KModel, iinv64));
+  else if constexpr (!LIT) m64 = karg_late<kf64x4>(kWideMdlOff + (int)offsetof(KModel, iinv64));
   const double ii0 = m64.x, ii1 = m64.y, ii2 = m64.z, im64 = m64.w;  // 1 / I_body, 1 / m
-#endif
   const float* xs = sh.xs();
   // ---- A: per step and axis, sum_b r_b x u_b and sum_b u_b; R, I_w^-1 and the instance scalars
   {
@@ -411,7 +398,7 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
         const double* ts = scr + S0 + 12 * k;
         const double xd = scr[18];
         // w = B_c u_k (+ Q_c f: f_est(3) into row 9)
-        const double w9 = ts[3] * ref_im64<NV, INST>(im64, ie) + scr[19];
+        const double w9 = ts[3] * ref_im64<NV, LIT, INST>(im64, ie) + scr[19];
         double c;
         if (j < 3 || (j >= 6 && j < 9)) {
           // j < 3: dt^2/2 (R' w[6:9])_j; 6..8: dt w_j, w[6:9] = I_w^-1 t
@@ -424,11 +411,11 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
         } else if (j == 3 || j == 9) {
           c = ((j == 3) ? dth : dt) * w9;
         } else if (j == 4 || j == 10) {
-          c = ((j == 4) ? dth : dt) * ts[4] * ref_im64<NV, INST>(im64, ie);
+          c = ((j == 4) ? dth : dt) * ts[4] * ref_im64<NV, LIT, INST>(im64, ie);
         } else if (j == 5) {
-          c = dth * ts[5] * ref_im64<NV, INST>(im64, ie) + dt3 * xd * w9;
+          c = dth * ts[5] * ref_im64<NV, LIT, INST>(im64, ie) + dt3 * xd * w9;
         } else {
-          c = dt * ts[5] * ref_im64<NV, INST>(im64, ie) + dth * xd * w9;
+          c = dt * ts[5] * ref_im64<NV, LIT, INST>(im64, ie) + dth * xd * w9;
         }
         // X_d,k-1 (x0 for k = 0: [rpy, p, w, v], rpy as quat_to_rpy in fp32)
         auto vprev = [&](int i) -> double {
@@ -522,7 +509,7 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
         // fp64 operands were the refining builds' register peak and spilled the J rows' neighbours)
         const int ic = (i < 3) ? i : 0, il = (i < 3) ? 0 : i - 3;
         const double x3 = (i == 3) ? xd : 0.0;
-        const double e2 = (dt * mu[9 + il] + dth * (mu[3 + il] + x3 * mu[11]) + dt3 * x3 * mu[5]) * ref_im64<NV, INST>(im64, ie);
+        const double e2 = (dt * mu[9 + il] + dth * (mu[3 + il] + x3 * mu[11]) + dt3 * x3 * mu[5]) * ref_im64<NV, LIT, INST>(im64, ie);
         __builtin_amdgcn_sched_barrier(0);
         double e1 = 0.0;
 #pragma unroll
@@ -540,11 +527,11 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
             ev += Ii[3 * i + m] * nu;
           }
         } else if (i == 3) {
-          ev = (dt * mu[9] + dth * (mu[3] + xd * mu[11]) + dt3 * xd * mu[5]) * ref_im64<NV, INST>(im64, ie);
+          ev = (dt * mu[9] + dth * (mu[3] + xd * mu[11]) + dt3 * xd * mu[5]) * ref_im64<NV, LIT, INST>(im64, ie);
         } else if (i == 4) {
-          ev = (dt * mu[10] + dth * mu[4]) * ref_im64<NV, INST>(im64, ie);
+          ev = (dt * mu[10] + dth * mu[4]) * ref_im64<NV, LIT, INST>(im64, ie);
         } else {
-          ev = (dt * mu[11] + dth * mu[5]) * ref_im64<NV, INST>(im64, ie);
+          ev = (dt * mu[11] + dth * mu[5]) * ref_im64<NV, LIT, INST>(im64, ie);
         }
       }
     }
@@ -554,17 +541,17 @@ __device__ __forceinline__ void refine_residual(const float* __restrict__ rec_in
   wbar();
 }
 
-template <int NV, bool INST = false>
+template <int NV, bool LIT, bool INST>
 __device__ __forceinline__ void wide_refine(const float* __restrict__ rec_in, const KParams& P, SharedW<NV>& sh,
                                             float (&slot)[WGeo<NV>::NH], float& xv, int q, int n, int wave,
-                                            const KInst* ie = nullptr) {
+                                            const KInst* ie) {
   using G = WGeo<NV>;
   constexpr int NH = G::NH;
   constexpr int NC = (NH + 63) / 64;
   const gfloat* rec = (const gfloat*)(rec_in);
   asm volatile("" : "+s"(rec));
   double* scr = reinterpret_cast<double*>(&sh.P[G::O_RINV]);
-  refine_residual<NV, INST>(rec_in, P, sh, wave, ie);
+  refine_residual<NV, LIT, INST>(rec_in, P, sh, wave, ie);
   // ---- E: row r's gradient entry, u = J2' r, x -= J2 u
   float rr = 0.f;
   {
@@ -653,11 +640,12 @@ __device__ __forceinline__ void wide_refine(const float* __restrict__ rec_in, co
 // (uniform over the workgroup): the model, f_max, 1 / mu, the weights and 2 alpha come from it by
 // scalar loads (inst_late), each where the shared build reads its own value, instead of P.mdl,
 // P.f_max, P.mu_inv, P.wts and P.alpha2.
-template <int NV, bool REFINE, bool INST = false>
+template <int NV, bool REFINE, bool LIT, bool INST>
 __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KParams& P,
                                         SharedW<NV>& sh, float* __restrict__ fout,
                                         uint8_t* __restrict__ st_out, int32_t* __restrict__ it_out,
-                                        const KInst* ie = nullptr) {
+                                        const KInst* ie) {
+  static_assert(!(LIT && INST), "a literal-model build has no per-instance twin");
   using G = WGeo<NV>;
   constexpr int NH = G::NH;
   constexpr int RQ = G::RQ;
@@ -725,13 +713,14 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
     for (int i = t; i < 6 * nfs; i += G::NT) sh.cflag[i] = 0;
   }
   Model md;
-#if CMPC_WIDE_LITERAL
-  constexpr KModel kLit{{.07f, 0.26f, 0.242f}, 1.f / 12.0f, {1.0 / 0.07, 1.0 / 0.26, 1.0 / 0.242}, 1.0 / 12.0};
-  make_model(srec, P.dt, kLit, md);
-#else
-  if constexpr (INST) make_model<kModelFromInst>(srec, P.dt, P.mdl, md, ie);
-  else make_model<kWideMdlOff>(srec, P.dt, P.mdl, md);
-#endif
+  if constexpr (LIT) {
+    constexpr KModel kLit{{.07f, 0.26f, 0.242f}, 1.f / 12.0f, {1.0 / 0.07, 1.0 / 0.26, 1.0 / 0.242}, 1.0 / 12.0};
+    make_model(srec, P.dt, kLit, md);
+  } else if constexpr (INST) {
+    make_model<kModelFromInst>(srec, P.dt, P.mdl, md, ie);
+  } else {
+    make_model<kWideMdlOff>(srec, P.dt, P.mdl, md);
+  }
   make_bdt<G::NT>(srec, md, t, sh.BdtT());
   wbar();
   float wts[13];
@@ -1108,50 +1097,50 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
           acc[m] = (lane + 64 * m < NV) ? sh.dfull()[(lane + 64 * m) < NV ? lane + 64 * m : 0] : 0.f;
           r_a[m] = 0.f;
         }
-#if CMPC_WIDE_WAVES_PER_EU <= 4
-        // software-pipelined: the LDS reads of step i - 1 are issued before step i's chain (the
-        // five-waves-per-SIMD builds keep the plain loop: 96 VGPRs leave no room for it)
-        float pd = 1.f, pv[RQ];
+        if constexpr (wide_waves(NV) <= 4) {
+          // software-pipelined: the LDS reads of step i - 1 are issued before step i's chain (the
+          // five-waves-per-SIMD builds keep the plain loop: 96 VGPRs leave no room for it)
+          float pd = 1.f, pv[RQ];
 #pragma unroll
-        for (int m = 0; m < RQ; m++) pv[m] = 0.f;
-        if (q > 0) {
-          const int off = rcol_w(q - 1);
-          pd = sh.P[off + q - 1];
+          for (int m = 0; m < RQ; m++) pv[m] = 0.f;
+          if (q > 0) {
+            const int off = rcol_w(q - 1);
+            pd = sh.P[off + q - 1];
 #pragma unroll
-          for (int m = 0; m < RQ; m++) pv[m] = (lane + 64 * m < q - 1) ? sh.P[off + lane + 64 * m] : 0.f;
-        }
-        for (int i = q - 1; i >= 0; i--) {
-          float pd_n = 1.f, pv_n[RQ];
-#pragma unroll
-          for (int m = 0; m < RQ; m++) pv_n[m] = 0.f;
-          if (i > 0) {
-            const int offn = rcol_w(i - 1);
-            pd_n = sh.P[offn + i - 1];
-#pragma unroll
-            for (int m = 0; m < RQ; m++) pv_n[m] = (lane + 64 * m < i - 1) ? sh.P[offn + lane + 64 * m] : 0.f;
+            for (int m = 0; m < RQ; m++) pv[m] = (lane + 64 * m < q - 1) ? sh.P[off + lane + 64 * m] : 0.f;
           }
-          const float ri = wdiv(rl_pos<RQ>(acc, i), pd);
+          for (int i = q - 1; i >= 0; i--) {
+            float pd_n = 1.f, pv_n[RQ];
 #pragma unroll
-          for (int m = 0; m < RQ; m++) {
-            const int pos = lane + 64 * m;
-            if (pos < i) acc[m] = fmaf(-pv[m], ri, acc[m]);
-            r_a[m] = (pos == i) ? ri : r_a[m];
-            pv[m] = pv_n[m];
-          }
-          pd = pd_n;
-        }
-#else
-        for (int i = q - 1; i >= 0; i--) {
-          const int off = rcol_w(i);
-          const float ri = wdiv(rl_pos<RQ>(acc, i), sh.P[off + i]);
+            for (int m = 0; m < RQ; m++) pv_n[m] = 0.f;
+            if (i > 0) {
+              const int offn = rcol_w(i - 1);
+              pd_n = sh.P[offn + i - 1];
 #pragma unroll
-          for (int m = 0; m < RQ; m++) {
-            const int pos = lane + 64 * m;
-            if (pos < i) acc[m] = fmaf(-sh.P[off + pos], ri, acc[m]);
-            r_a[m] = (pos == i) ? ri : r_a[m];
+              for (int m = 0; m < RQ; m++) pv_n[m] = (lane + 64 * m < i - 1) ? sh.P[offn + lane + 64 * m] : 0.f;
+            }
+            const float ri = wdiv(rl_pos<RQ>(acc, i), pd);
+#pragma unroll
+            for (int m = 0; m < RQ; m++) {
+              const int pos = lane + 64 * m;
+              if (pos < i) acc[m] = fmaf(-pv[m], ri, acc[m]);
+              r_a[m] = (pos == i) ? ri : r_a[m];
+              pv[m] = pv_n[m];
+            }
+            pd = pd_n;
+          }
+        } else {
+          for (int i = q - 1; i >= 0; i--) {
+            const int off = rcol_w(i);
+            const float ri = wdiv(rl_pos<RQ>(acc, i), sh.P[off + i]);
+#pragma unroll
+            for (int m = 0; m < RQ; m++) {
+              const int pos = lane + 64 * m;
+              if (pos < i) acc[m] = fmaf(-sh.P[off + pos], ri, acc[m]);
+              r_a[m] = (pos == i) ? ri : r_a[m];
+            }
           }
         }
-#endif
       }
       if (wave == 0) {
         float t1w = kBigF;
@@ -1397,7 +1386,7 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
     rinv_ok = false;  // the R^-1 area is the refinement's scratch from here on
     it_refined = iters;
     passes++;
-    wide_refine<NV, INST>(rec, P, sh, slot, xv, q, n, wave, ie);
+    wide_refine<NV, LIT, INST>(rec, P, sh, slot, xv, q, n, wave, ie);
    }
   }
 
@@ -1448,8 +1437,7 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
 
 }  // namespace
 
-// Two launch forms per class (CMPC_WIDE_BUILD per width unit: 1 one-per-entry, 2 persistent,
-// 3 both):
+// Two launch forms (WideBuild::persistent, cmpc_wide_builds.h):
 //   * one workgroup per possible list entry (the list length is only known on the device);
 //     surplus workgroups exit after one load. No loop around the solve, so nothing is carried
 //     across instances. But an empty or sparse class drains up to `batch` empty workgroups: 3.5 ms
@@ -1458,39 +1446,32 @@ __device__ __forceinline__ void solve_w(const float* __restrict__ rec, const KPa
 //     (hipOccupancyMaxActiveBlocksPerMultiprocessor x CUs), each dequeuing list entries with one
 //     global atomic until the list is exhausted. The loop costs the populous classes registers
 //     (80 / 96 / 128: 11 / 20 / 4 spilled VGPRs).
-// launch_solve asks for the one-per-entry form (deq == nullptr) only for the class that holds the
-// trot size n = 6N (the mode of any contact mix: every instance at config 3 / N = 16 / N = 20
-// trot), the persistent form for every other class. The 144 / 192 / 256 classes are built
-// persistent only (no spills at their occupancy); their single-instance path runs the loop once
-// (deq == nullptr: workgroup i takes entry i).
-#ifndef CMPC_WIDE_BUILD
-#define CMPC_WIDE_BUILD 1
-#endif
-
-// REFINE is part of the kernel's name: the refining and plain builds of a class live in different
-// units, and one instantiation name would let the linker keep only one of them
-// (LIT, the literal-model build, is part of the name for the same reason)
-template <int NV, bool PERSIST, bool REFINE, bool LIT = (CMPC_WIDE_LITERAL != 0)>
-__global__ __launch_bounds__(WGeo<NV>::NT, CMPC_WIDE_WAVES_PER_EU) void cmpc_solve_w_kernel(
-    WideArgs A) {
+// plan_solve asks for the one-per-entry form only for the class that holds the trot size n = 6N
+// (the mode of any contact mix: every instance at config 3 / N = 16 / N = 20 trot), the persistent
+// form for every other class. The 144 / 192 / 256 classes are built persistent only (no spills at
+// their occupancy); their single-instance path runs the loop once (a null dequeue counter:
+// workgroup i takes entry i).
+// Every template argument is part of the kernel's name: the builds of a class live in different
+// units, and one instantiation name would let the linker keep only one of them.
+template <int NV, bool PERSIST, bool REFINE, bool LIT>
+__global__ __launch_bounds__(WGeo<NV>::NT, wide_waves(NV)) void cmpc_solve_w_kernel(WideArgs A) {
   // kWideMdlOff counts from the head of the argument segment: WideArgs is argument 0
   using KA = KArg<0, decltype(&cmpc_solve_w_kernel<NV, PERSIST, REFINE, LIT>)>;
   static_assert(std::is_same<typename KA::type, WideArgs>::value && KA::offset() == 0, "WideArgs leads the arguments");
   __shared__ SharedW<NV> sh;
-#if CMPC_WIDE_PRIO > 0
   // issue priority of this workgroup's waves over the class-1 waves sharing their SIMDs
-  __builtin_amdgcn_s_setprio(CMPC_WIDE_PRIO);
-#endif
+  if constexpr (wide_prio(REFINE) > 0) __builtin_amdgcn_s_setprio(wide_prio(REFINE));
   const int count = *A.in_count;
   if constexpr (!PERSIST) {  // one workgroup per possible list entry
     const int b = blockIdx.x;
     if (b >= count) return;
     const int inst = A.in_list[b];
-    solve_w<NV, REFINE>(A.recs + (size_t)inst * A.P.rec_words, A.P, sh, A.forces + (size_t)inst * A.P.out_cols,
-                        A.status + inst, A.iters ? A.iters + inst : nullptr);
+    solve_w<NV, REFINE, LIT, false>(A.recs + (size_t)inst * A.P.rec_words, A.P, sh,
+                                    A.forces + (size_t)inst * A.P.out_cols, A.status + inst,
+                                    A.iters ? A.iters + inst : nullptr, nullptr);
   } else {
     for (int round = 0;; round++) {
-      // deq == nullptr (single-instance path): workgroup i takes entry i, once
+      // deq == nullptr (a launch that wants one workgroup per entry): workgroup i takes entry i, once
       // base: entries below it belong to a one-per-entry launch of a predicted grid (this launch
       // takes the rest, cmpc_launch.hip hint); 0 otherwise
       if (threadIdx.x == 0) sh.deq_b = A.base + (A.deq ? atomicAdd(A.deq, 1) : (round == 0 ? (int)blockIdx.x : count));
@@ -1498,8 +1479,9 @@ __global__ __launch_bounds__(WGeo<NV>::NT, CMPC_WIDE_WAVES_PER_EU) void cmpc_sol
       const int b = __builtin_amdgcn_readfirstlane(sh.deq_b);
       if (b >= count) break;
       const int inst = A.in_list[b];
-      solve_w<NV, REFINE>(A.recs + (size_t)inst * A.P.rec_words, A.P, sh, A.forces + (size_t)inst * A.P.out_cols,
-                          A.status + inst, A.iters ? A.iters + inst : nullptr);
+      solve_w<NV, REFINE, LIT, false>(A.recs + (size_t)inst * A.P.rec_words, A.P, sh,
+                                      A.forces + (size_t)inst * A.P.out_cols, A.status + inst,
+                                      A.iters ? A.iters + inst : nullptr, nullptr);
       wbar();  // every wave is done with this instance's LDS before the next record lands there
     }
   }
@@ -1509,21 +1491,21 @@ __global__ __launch_bounds__(WGeo<NV>::NT, CMPC_WIDE_WAVES_PER_EU) void cmpc_sol
 // same two launch forms with the instance's table entry handed to the solve. A kernel of its own
 // name, so the shared build keeps its name and its registers; not built in the literal-model units,
 // which a handle with a table never launches (the host clears KParams::mdl_default).
-#if !CMPC_WIDE_LITERAL
+// (The body is written out a second time on purpose: with both kernels as wrappers over one
+// force-inlined body the compiler emitted other code for every build, two basic blocks fewer and
+// another schedule, and the builds are held to the assembly they were measured with.)
 template <int NV, bool PERSIST, bool REFINE>
-__global__ __launch_bounds__(WGeo<NV>::NT, CMPC_WIDE_WAVES_PER_EU) void cmpc_solve_w_inst_kernel(
-    WideArgs A) {
+__global__ __launch_bounds__(WGeo<NV>::NT, wide_waves(NV)) void cmpc_solve_w_inst_kernel(WideArgs A) {
   __shared__ SharedW<NV> sh;
-#if CMPC_WIDE_PRIO > 0
-  __builtin_amdgcn_s_setprio(CMPC_WIDE_PRIO);
-#endif
+  if constexpr (wide_prio(REFINE) > 0) __builtin_amdgcn_s_setprio(wide_prio(REFINE));
   const int count = *A.in_count;
   if constexpr (!PERSIST) {
     const int b = blockIdx.x;
     if (b >= count) return;
     const int inst = A.in_list[b];
-    solve_w<NV, REFINE, true>(A.recs + (size_t)inst * A.P.rec_words, A.P, sh, A.forces + (size_t)inst * A.P.out_cols,
-                              A.status + inst, A.iters ? A.iters + inst : nullptr, inst_entry(A.P, inst));
+    solve_w<NV, REFINE, false, true>(A.recs + (size_t)inst * A.P.rec_words, A.P, sh,
+                                     A.forces + (size_t)inst * A.P.out_cols, A.status + inst,
+                                     A.iters ? A.iters + inst : nullptr, inst_entry(A.P, inst));
   } else {
     for (int round = 0;; round++) {
       if (threadIdx.x == 0) sh.deq_b = A.base + (A.deq ? atomicAdd(A.deq, 1) : (round == 0 ? (int)blockIdx.x : count));
@@ -1531,32 +1513,31 @@ __global__ __launch_bounds__(WGeo<NV>::NT, CMPC_WIDE_WAVES_PER_EU) void cmpc_sol
       const int b = __builtin_amdgcn_readfirstlane(sh.deq_b);
       if (b >= count) break;
       const int inst = A.in_list[b];
-      solve_w<NV, REFINE, true>(A.recs + (size_t)inst * A.P.rec_words, A.P, sh,
-                                A.forces + (size_t)inst * A.P.out_cols, A.status + inst,
-                                A.iters ? A.iters + inst : nullptr, inst_entry(A.P, inst));
+      solve_w<NV, REFINE, false, true>(A.recs + (size_t)inst * A.P.rec_words, A.P, sh,
+                                       A.forces + (size_t)inst * A.P.out_cols, A.status + inst,
+                                       A.iters ? A.iters + inst : nullptr, inst_entry(A.P, inst));
       wbar();
     }
   }
 }
-#endif
 
-// (INST: the grid cap of the per-instance build, whose occupancy may differ)
-template <int NV, bool PERSIST, bool REFINE, bool INST = false>
+namespace {
+
+// workgroups of a persistent launch at most: what fits the GPU at the kernel's occupancy. Internal
+// linkage and every kernel argument in its own: each kernel of each unit has a cap of its own
+// (INST: the per-instance twin, whose occupancy may differ)
+template <int NV, bool REFINE, bool LIT, bool INST>
 int wide_grid_cap() {
   static const int cap = [] {
     int nb = 0, dev = 0, cus = 0;
     hipError_t oe;
-#if !CMPC_WIDE_LITERAL
     if constexpr (INST)
-      oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, cmpc_solve_w_inst_kernel<NV, PERSIST, REFINE>,
+      oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, cmpc_solve_w_inst_kernel<NV, true, REFINE>,
                                                         WGeo<NV>::NT, 0);
     else
-#endif
-      oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, cmpc_solve_w_kernel<NV, PERSIST, REFINE>, WGeo<NV>::NT,
-                                                        0);
-    if (oe != hipSuccess ||
-        nb <= 0)
-      nb = 1;
+      oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, cmpc_solve_w_kernel<NV, true, REFINE, LIT>,
+                                                        WGeo<NV>::NT, 0);
+    if (oe != hipSuccess || nb <= 0) nb = 1;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
       cus = 256;
@@ -1565,50 +1546,34 @@ int wide_grid_cap() {
   return cap;
 }
 
-// deq != nullptr: persistent form (if built) with that dequeue counter; nullptr: one workgroup per
-// entry (if built; the persistent-only classes then run the loop once per workgroup). Internal
-// linkage: the width units compile it with different CMPC_WIDE_BUILD, and one shared
-// instantiation would serve both launch forms with whichever the linker kept.
-namespace {
-template <int NV>
-hipError_t launch_wide_impl(const float* d_recs, const KParams& P, float* d_forces,
-                            uint8_t* d_status, int32_t* d_iters, const int* in_list,
-                            const int* in_count, int* deq, int grid, hipStream_t stream, int base = 0) {
+}  // namespace
+
+// The launcher of one build (declared in cmpc_kernels.h; instantiated once, in the build's unit).
+// The launch form is the build's: PERSIST with a dequeue counter runs up to wide_grid_cap
+// workgroups over the list, PERSIST with c.deq == nullptr one workgroup per entry, each through
+// the loop once. A handle with a per-instance table (P.inst) gets the per-instance twin in the same
+// form.
+template <int NV, bool PERSIST, bool REFINE, bool LIT>
+hipError_t launch_wide_build(const KParams& P, const WideCall& c) {
+  static_assert(wide_build_row({NV, PERSIST, REFINE, LIT}) >= 0, "a row of kWideBuild");
+  int grid = c.grid;
   if (grid <= 0) return hipSuccess;
-  constexpr bool kOne = (CMPC_WIDE_BUILD & 1) != 0, kPersist = (CMPC_WIDE_BUILD & 2) != 0;
-  const bool persist = kPersist && (deq != nullptr || !kOne);
-  WideArgs A{d_recs, d_forces, d_status, d_iters, in_list, in_count, persist ? deq : nullptr, P, base};
-#if !CMPC_WIDE_LITERAL
-  if (P.inst) {  // the per-instance builds, in the same two launch forms
-    constexpr bool kRef = CMPC_WIDE_REFINE != 0;
-    if (persist) {
-      if constexpr (kPersist) {
-        if (deq) grid = grid < wide_grid_cap<NV, true, kRef, true>() ? grid : wide_grid_cap<NV, true, kRef, true>();
-        hipLaunchKernelGGL((cmpc_solve_w_inst_kernel<NV, true, kRef>), dim3(grid), dim3(WGeo<NV>::NT), 0, stream, A);
-      }
+  WideArgs A{c.recs, c.forces, c.status, c.iters, c.list, c.count, PERSIST ? c.deq : nullptr, P, c.base};
+  if (P.inst) {
+    if constexpr (LIT) {
+      return hipErrorInvalidValue;  // a literal-model build is never taken while a table is set
     } else {
-      if constexpr (kOne)
-        hipLaunchKernelGGL((cmpc_solve_w_inst_kernel<NV, false, kRef>), dim3(grid), dim3(WGeo<NV>::NT), 0, stream, A);
+      if constexpr (PERSIST)
+        if (c.deq && grid > wide_grid_cap<NV, REFINE, false, true>()) grid = wide_grid_cap<NV, REFINE, false, true>();
+      hipLaunchKernelGGL((cmpc_solve_w_inst_kernel<NV, PERSIST, REFINE>), dim3(grid), dim3(WGeo<NV>::NT), 0, c.stream,
+                         A);
+      return hipGetLastError();
     }
-    return hipGetLastError();
   }
-#else
-  if (P.inst) return hipErrorInvalidValue;  // a literal-model build is never taken while a table is set
-#endif
-  if (persist) {
-    if constexpr (kPersist) {
-      constexpr bool kRef = CMPC_WIDE_REFINE != 0;
-      if (deq) grid = grid < wide_grid_cap<NV, true, kRef>() ? grid : wide_grid_cap<NV, true, kRef>();
-      hipLaunchKernelGGL((cmpc_solve_w_kernel<NV, true, CMPC_WIDE_REFINE != 0>), dim3(grid), dim3(WGeo<NV>::NT), 0,
-                         stream, A);
-    }
-  } else {
-    if constexpr (kOne)
-      hipLaunchKernelGGL((cmpc_solve_w_kernel<NV, false, CMPC_WIDE_REFINE != 0>), dim3(grid), dim3(WGeo<NV>::NT), 0,
-                         stream, A);
-  }
+  if constexpr (PERSIST)
+    if (c.deq && grid > wide_grid_cap<NV, REFINE, LIT, false>()) grid = wide_grid_cap<NV, REFINE, LIT, false>();
+  hipLaunchKernelGGL((cmpc_solve_w_kernel<NV, PERSIST, REFINE, LIT>), dim3(grid), dim3(WGeo<NV>::NT), 0, c.stream, A);
   return hipGetLastError();
 }
-}  // namespace
 
 }  // namespace cmpc

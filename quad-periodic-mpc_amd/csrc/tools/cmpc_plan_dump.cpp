@@ -2,6 +2,8 @@
 // order launch_solve issues it. Plain C++: no HIP, no library (tests/test_launch_plan.py).
 //   cmpc_plan_dump N refine batch due [hint ints ...]   hint: the kHdr ints of a solve's header
 //   cmpc_plan_dump classes n_max   size_class(n, ...) for n = 0..n_max, every (c1_max, c1_listed, tail)
+//   cmpc_plan_dump builds           the rows of kWideBuild (cmpc_wide_builds.h)
+//   cmpc_plan_dump select           the build a launch takes, for every (wide class, form, refine, mdl_default)
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -21,10 +23,40 @@ static int dump_classes(int n_max) {
   return 0;
 }
 
+static void print_build(const WideBuild& b) {
+  printf("w%d form=%s refine=%d literal=%d\n", b.nv, b.persistent ? "persistent" : "one_per_entry", b.refine,
+         b.literal);
+}
+
+static int dump_builds() {
+  for (const WideBuild& b : kWideBuild) print_build(b);
+  return 0;
+}
+
+static int dump_select() {
+  for (int c = kW80; c <= kW256; c++)
+    for (int persistent = 0; persistent < 2; persistent++)
+      for (int refine = 0; refine < 2; refine++)
+        for (int dflt = 0; dflt < 2; dflt++) {
+          const int row = select_wide_build(kClass[c].width, persistent != 0, refine != 0, dflt != 0);
+          printf("w%d want=%s refine=%d mdl_default=%d -> ", kClass[c].width,
+                 persistent ? "persistent" : "one_per_entry", refine, dflt);
+          if (row < 0) {
+            printf("none\n");
+            return 1;
+          }
+          print_build(kWideBuild[row]);
+        }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc == 3 && !strcmp(argv[1], "classes")) return dump_classes(atoi(argv[2]));
+  if (argc == 2 && !strcmp(argv[1], "builds")) return dump_builds();
+  if (argc == 2 && !strcmp(argv[1], "select")) return dump_select();
   if (argc != 5 && argc != 5 + kHdr) {
-    fprintf(stderr, "usage: %s N refine batch due [%d hint ints] | %s classes n_max\n", argv[0], kHdr, argv[0]);
+    fprintf(stderr, "usage: %s N refine batch due [%d hint ints] | %s classes n_max | %s builds | %s select\n", argv[0],
+            kHdr, argv[0], argv[0], argv[0]);
     return 2;
   }
   const int N = atoi(argv[1]), refine = atoi(argv[2]), batch = atoi(argv[3]), due = atoi(argv[4]);

@@ -1,6 +1,6 @@
 """Register table of the kernels from two compile logs taken with
-``-Rpass-analysis=kernel-resource-usage`` (one "=== <source>" line per translation unit, then the
-compiler's remarks): per kernel VGPRs, SGPRs, scratch bytes per lane, occupancy and spill counts,
+``-Rpass-analysis=kernel-resource-usage`` (one "=== <source>[+<define>]" line per translation unit
+of build.py's UNITS, then the compiler's remarks): per kernel VGPRs, SGPRs, scratch bytes per lane, occupancy and spill counts,
 before -> after, as a markdown table.
 
 usage: python scripts/resource_table.py BEFORE.log AFTER.log
@@ -21,16 +21,27 @@ def demangle(names):
         n = re.sub(r"^void ", "", n)
         n = re.sub(r"\(.*$", "", n)   # the name without its argument list
         # the wide kernels' fourth argument (the literal-model build) is not part of the comparison:
-        # a literal build (unit *rd.hip) is compared with the parent's build of the same class
+        # a literal build (row NV,P,R,1) is compared with the parent's build of the same class
         short.append(re.sub(r"(cmpc_solve_w_kernel<\d+, \w+, \w+), \w+>", r"\1>", n))
     return short
+
+
+def unit(tu):
+    """A log's unit label as the row of kWideBuild it builds: a log from before the build table names
+    the wide units cmpc_wide_w<NV>[p][r][d].hip (128 and up were built refining without the r)."""
+    m = re.fullmatch(r"cmpc_wide_w(\d+)(p?)(r?)(d?)\.hip", tu)
+    if not m:
+        return tu
+    nv = int(m.group(1))
+    return "cmpc_wide_unit.hip+CMPC_UNIT_WIDE=%d,%d,%d,%d" % (nv, bool(m.group(2)) or nv > 128,
+                                                             bool(m.group(3)) or nv > 120, bool(m.group(4)))
 
 
 def parse(path):
     table, tu, cur = {}, "?", None
     for line in open(path, errors="replace"):
         if line.startswith("=== "):
-            tu = line[4:].strip()
+            tu = unit(line[4:].strip())
             continue
         m = re.search(r"remark:\s+(.*?): (.*?) \[-Rpass-analysis", line)
         if not m:
@@ -54,7 +65,7 @@ def main():
     changed = 0
     for tu, name in sorted(after):
         a = after[(tu, name)]
-        b = before.get((tu, name)) or before.get((re.sub(r"rd\.hip$", "r.hip", tu), name), {})
+        b = before.get((tu, name)) or before.get((re.sub(r"(WIDE=\d+,\d,\d),1$", r"\1,0", tu), name), {})
         cells = []
         for f, _ in FIELDS:
             x, y = b.get(f, "-"), a.get(f, "-")

@@ -144,3 +144,49 @@ def test_size_class_sweep(dump):
                 assert [int(x) for x in body.split()] == [parent_chain(n, c1_max, c1_listed, tail_on)
                                                           for n in range(241)]
     assert next(rows, None) is None
+
+
+# ---- the builds of the wide kernel template (csrc/cmpc_wide_builds.h) and the choice among them
+def build_line(width, form, refine, literal):
+    return f"w{width} form={form} refine={refine} literal={literal}"
+
+
+def test_wide_build_table(dump):
+    """The 21 builds, as the 21 cmpc_wide_w*.hip units of commit ec0c88f stood: 80 both forms x both
+    refine values; 96 and 120 those four and the two refining forms with the literal model; 128
+    refining, both forms; 144, 192 and 256 refining, persistent only."""
+    expected = [build_line(80, f, r, 0) for r in (0, 1) for f in (ONE, PERSIST)]
+    for width in (96, 120):
+        expected += [build_line(width, f, r, 0) for r in (0, 1) for f in (ONE, PERSIST)]
+        expected += [build_line(width, f, 1, 1) for f in (ONE, PERSIST)]
+    expected += [build_line(128, f, 1, 0) for f in (ONE, PERSIST)]
+    expected += [build_line(width, PERSIST, 1, 0) for width in (144, 192, 256)]
+    assert len(expected) == 21
+    got = dump("builds")
+    assert len(got) == len(set(got)) == 21
+    assert sorted(got) == sorted(expected)
+
+
+def parent_launcher(width, persistent, refine, mdl_default):
+    """The build that the if-chains of the units cmpc_wide_w{80,96,120,128,144,192,256}.hip at commit
+    ec0c88f forwarded to (persistent: deq != nullptr), literally, as (form, refine, literal)."""
+    if width == 80:            # launch_wide_w80: _persist_r / _r on P.refine, else _persist / its own
+        return (PERSIST if persistent else ONE, refine, 0)
+    if width in (96, 120):     # the same chain, _lit on P.mdl_default under P.refine
+        return (PERSIST if persistent else ONE, refine, 1 if (refine and mdl_default) else 0)
+    if width == 128:           # launch_wide_w128: _persist on deq, else its own; both built refining
+        return (PERSIST if persistent else ONE, 1, 0)
+    return (PERSIST, 1, 0)     # 144, 192, 256: one unit each, persistent only, refining
+
+
+def test_wide_build_selection(dump):
+    expected = []
+    for width in (80, 96, 120, 128, 144, 192, 256):
+        for persistent in (0, 1):
+            for refine in (0, 1):
+                for mdl_default in (0, 1):
+                    expected.append(f"w{width} want={PERSIST if persistent else ONE} refine={refine} "
+                                    f"mdl_default={mdl_default} -> "
+                                    + build_line(width, *parent_launcher(width, persistent, refine, mdl_default)))
+    assert len(expected) == 56
+    assert dump("select") == expected
