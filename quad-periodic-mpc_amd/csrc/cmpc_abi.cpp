@@ -8,9 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <complex>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <array>
 #include <mutex>
@@ -19,6 +17,7 @@
 #include <vector>
 
 #include "../../include/cmpc_solver.h"
+#include "cmpc_host_buffers.h"
 #include "cmpc_kernels.h"
 
 namespace {
@@ -28,54 +27,93 @@ int fail(const char* what, hipError_t e) {
   g_last_error = std::string(what) + ": " + hipGetErrorString(e);
   return -(int)e - 1000;
 }
+
+// 0, or fail(what, e)
+int checked(const char* what, hipError_t e) { return e == hipSuccess ? 0 : fail(what, e); }
+
+int bad_arguments(const char* who) {
+  g_last_error = std::string(who) + ": bad arguments";
+  return -1;
+}
+
+// the two allocators of cmpc::Owned (cmpc_host_buffers.h)
+struct DeviceAlloc {
+  static hipError_t alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+  static void release(void* p) { (void)hipFree(p); }
+};
+struct PinnedAlloc {
+  static hipError_t alloc(void** p, size_t bytes, unsigned flags = hipHostMallocDefault) {
+    return hipHostMalloc(p, bytes, flags);
+  }
+  static void release(void* p) { (void)hipHostFree(p); }
+};
+template <class T> using DevBuf = cmpc::Owned<T, DeviceAlloc>;
+template <class T> using PinBuf = cmpc::Owned<T, PinnedAlloc>;
+using Stage = cmpc::SingleStage;
 }  // namespace
 
-struct cmpc_batch {
+// The default robot: m = 12, I_body = diag(.07, .26, .242) (RobotState.h:25-26)
+static const cmpc_model kDefaultModel = {12.0, {0.07, 0.26, 0.242}};
+
+// (hidden: the handle is opaque to callers, and its destructor is no export of the library)
+struct __attribute__((visibility("hidden"))) cmpc_batch {
   cmpc_params prm;
-  cmpc_model model = {12.0, {0.07, 0.26, 0.242}};  // cmpc_batch_set_model; kept across set_params
-  cmpc::KParams kp;
+  cmpc_model model = kDefaultModel;  // cmpc_batch_set_model; kept across set_params
+  cmpc::KParams kp;              // rebuilt from the four fields around it by rebuild_kparams alone
   int out_steps = 0;             // cmpc_batch_set_output_steps (0: every step)
   int refine = 1;                // cmpc_batch_set_refine (1: from N = 11, 0: off)
   int max_batch = 0;
   hipStream_t stream = nullptr;
   bool own_stream = false;
-  int* d_work = nullptr;
-  float* d_gauss = nullptr;      // gaussian_filter kernels of the config-5 estimator
+  DevBuf<int> d_work;
+  DevBuf<float> d_gauss;         // gaussian_filter kernels of the config-5 estimator
   // per-instance table (cmpc_batch_set_instance_params): kernel-side entries, the snapshot of the
   // caller's rows and the validation kernel's counter, allocated for max_batch by the first call
-  cmpc::KInst* d_inst = nullptr;
-  double* d_inst_rows = nullptr;
-  int* d_inst_bad = nullptr;
+  DevBuf<cmpc::KInst> d_inst;
+  DevBuf<double> d_inst_rows;
+  DevBuf<int> d_inst_bad;
   int inst_count = 0;            // rows of the parameter table in force (0: none)
   int cost_count = 0;            // rows of the cost table in force (cmpc_batch_set_instance_costs; 0: none)
                                  // (kp.inst is null when both are 0)
-  double* d_admm_slabs = nullptr;  // ADMM inverses of QPs with n > 120 (cmpc_admm.hip)
+  DevBuf<double> d_admm_slabs;   // ADMM inverses of QPs with n > 120 (cmpc_admm.hip)
   size_t admm_slab_doubles = 0;
   int admm_nslabs = 0;
   bool admm_used = false;        // slabs are allocated on the first ADMM call, not at create
   bool staged = false;           // every allocation of ensure_staging succeeded
-  float* d_admm_H = nullptr;     // condensed qH / qg staging of the single-instance ADMM path
+  DevBuf<float> d_admm_H;        // condensed qH / qg staging of the single-instance ADMM path
   // staging for the host-pointer entry point (allocated lazily, sized max_batch)
-  float* d_rec = nullptr;
-  float* d_forces = nullptr;
-  uint8_t* d_status = nullptr;
-  int32_t* d_iters = nullptr;
+  DevBuf<float> d_rec;
+  DevBuf<float> d_forces;
+  DevBuf<uint8_t> d_status;
+  DevBuf<int32_t> d_iters;
   // single-instance fast path of cmpc_batch_solve_host: the one-entry instance list {1, 0}, the
-  // instance's forces + status word (one D2H), pinned host staging of record and result
-  int* d_one = nullptr;
-  float* d_single_out = nullptr;
-  float* h_pin = nullptr;
+  // instance's forces + status word (one D2H), pinned host staging of record and result (Stage)
+  DevBuf<int> d_one;
+  DevBuf<float> d_single_out;
+  PinBuf<float> h_pin;
   // outputs of cmpc_batch_evaluate_host (allocated on its first call, sized max_batch)
-  float* d_xpred = nullptr;
-  double* d_cert = nullptr;
+  DevBuf<float> d_xpred;
+  DevBuf<double> d_cert;
   // side streams + fork/join events for the wider size classes (cmpc_launch.hip)
   cmpc::LaunchCtx ctx;
+  PinBuf<int> h_hint;            // ctx.h_hint: freed after the own stream is idle (cmpc_batch_destroy)
   bool pooled_sides = false;     // ctx.side came from the process-wide pool (acquire_sides)
   // optional per-launch timing (cmpc_batch_enable_timing)
   std::vector<hipEvent_t> ev;
   int ev_steps = 0, ev_next = 0;
   int ev_every = 1, ev_solves = 0;  // events on every ev_every-th solve (cmpc_batch_enable_timing_every)
 };
+
+// copies on the handle's stream and its synchronisation: 0, or the failure's code with its text set
+static int stream_h2d(cmpc_batch* h, void* dst, const void* src, size_t bytes) {
+  return checked("H2D", hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
+}
+static int stream_d2h(cmpc_batch* h, void* dst, const void* src, size_t bytes) {
+  return checked("D2H", hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
+}
+static int stream_sync(cmpc_batch* h) {
+  return checked("sync", hipStreamSynchronize(h->stream));
+}
 
 constexpr int CMPC_REFINE_FROM_N = 11;  // first horizon whose wide classes refine
 
@@ -131,9 +169,6 @@ void release_sides(const std::array<hipStream_t, cmpc::kSideStreams>& s) {
 }
 }  // namespace
 
-// The default robot: m = 12, I_body = diag(.07, .26, .242) (RobotState.h:25-26)
-static const cmpc_model kDefaultModel = {12.0, {0.07, 0.26, 0.242}};
-
 // The kernels' form of the model, every derived value formed here once. The fp32 kernels get
 // (float) of each field and 1.f / (float) mass, the fp64 paths the reciprocals of the doubles:
 // for the default these are the values the literals .07f, 1.f / 12.0f, 1.0 / 0.07 and 1.0 / 12.0
@@ -160,10 +195,12 @@ static bool model_ok(const cmpc_model& m) {
   return fin;
 }
 
-static cmpc::KParams make_kparams(const cmpc_params& p, const cmpc_model& m) {
+// Every derived field of the kernels' parameters, from the four things a handle is set to: pure, so
+// rebuilding all of it where one of them changed gives the same bits as updating that field alone.
+// (kp.inst and, with it, kp.mdl_default are the tables' part: apply_inst.)
+static cmpc::KParams make_kparams(const cmpc_params& p, const cmpc_model& m, int out_steps, int refine) {
   cmpc::KParams k{};
   k.mdl = make_kmodel(m);
-  k.mdl_default = std::memcmp(&m, &kDefaultModel, sizeof m) == 0;
   k.dt = p.dt;
   k.mu_inv = 1.f / p.mu;  // fpt mu = 1.f / setup->mu (SolverMPC.cpp:657)
   k.f_max = p.f_max;
@@ -174,11 +211,11 @@ static cmpc::KParams make_kparams(const cmpc_params& p, const cmpc_model& m) {
   k.max_iter = p.max_iter > 0 ? p.max_iter : 100;
   // the fp32 pipelines of the reference and of this solver are within ~1e-5 of the exact optimum
   // at N <= 10 and drift to ~1e-4 beyond: the refinement runs from N = 11
-  k.refine = p.horizon >= CMPC_REFINE_FROM_N ? 1 : 0;
+  k.refine = (refine && p.horizon >= CMPC_REFINE_FROM_N) ? 1 : 0;
   k.dt64 = (double)k.dt;
   k.dth64 = 0.5 * k.dt64 * k.dt64;
   k.dt3_64 = k.dt64 * k.dt64 * k.dt64 / 6.0;
-  k.out_cols = 12 * p.horizon;
+  k.out_cols = 12 * ((out_steps > 0 && out_steps < p.horizon) ? out_steps : p.horizon);
   return k;
 }
 
@@ -211,12 +248,10 @@ static int ensure_admm_slabs(cmpc_batch* h) {
   const int ns = h->max_batch < cmpc::kAdmmSlabs ? h->max_batch : cmpc::kAdmmSlabs;
   const size_t need = (size_t)ns * cmpc::admm_slab_doubles(h->prm.horizon);
   if (need <= h->admm_slab_doubles && h->admm_nslabs >= ns) return 0;
-  if (h->d_admm_slabs) (void)hipFree(h->d_admm_slabs);
-  h->d_admm_slabs = nullptr;
   h->admm_slab_doubles = 0;
   h->admm_nslabs = 0;
-  hipError_t e = hipMalloc(&h->d_admm_slabs, need * sizeof(double));
-  if (e != hipSuccess) return fail("hipMalloc(ADMM slabs)", e);
+  // (the smaller slabs are released first)
+  if (int r = checked("hipMalloc(ADMM slabs)", h->d_admm_slabs.alloc(need))) return r;
   h->admm_slab_doubles = need;
   h->admm_nslabs = ns;
   return 0;
@@ -228,15 +263,21 @@ static int ensure_admm_slabs(cmpc_batch* h) {
 // now stand: a kernel on the handle's stream, behind every earlier call and ahead of every later
 // one, no allocation, no host synchronisation.
 static int apply_inst(cmpc_batch* h) {
-  h->kp.inst = (h->inst_count > 0 || h->cost_count > 0) ? h->d_inst : nullptr;
+  h->kp.inst = (h->inst_count > 0 || h->cost_count > 0) ? h->d_inst.get() : nullptr;
   h->kp.mdl_default = !h->kp.inst && std::memcmp(&h->model, &kDefaultModel, sizeof h->model) == 0;
   if (!h->kp.inst || (h->inst_count > 0 && h->cost_count > 0)) return 0;
   const bool model_half = h->inst_count == 0;
-  const hipError_t e =
-      cmpc::launch_inst_fill(h->d_inst, h->d_inst_rows, model_half ? h->cost_count : h->inst_count, model_half,
-                             h->kp, h->model, (double)h->prm.mu, (double)h->prm.f_max, h->prm.alpha, h->stream);
-  if (e != hipSuccess) return fail("launch_inst_fill", e);
-  return 0;
+  return checked("launch_inst_fill",
+                 cmpc::launch_inst_fill(h->d_inst.get(), h->d_inst_rows.get(), model_half ? h->cost_count : h->inst_count,
+                                        model_half, h->kp, h->model, (double)h->prm.mu, (double)h->prm.f_max,
+                                        h->prm.alpha, h->stream));
+}
+
+// h->kp from the handle's prm, model, out_steps and refine, then the tables' view of it: what every
+// setter of one of the four calls, so no derived field is stated anywhere else
+static int rebuild_kparams(cmpc_batch* h) {
+  h->kp = make_kparams(h->prm, h->model, h->out_steps, h->refine);
+  return apply_inst(h);
 }
 
 // a batch the handle can take: within max_batch and, with a per-instance table, within its rows
@@ -249,20 +290,17 @@ static bool batch_ok(const cmpc_batch* h, int batch) {
 // 48 B of row snapshot per instance, and the validation kernels' counter
 static int ensure_inst_buffers(cmpc_batch* h) {
   if (h->d_inst) return 0;
+  DevBuf<cmpc::KInst> ent;
+  DevBuf<double> rows;
+  DevBuf<int> bad;
   hipError_t e;
-  cmpc::KInst* ent = nullptr;
-  double* rows = nullptr;
-  int* bad = nullptr;
-  if ((e = hipMalloc(&ent, sizeof(cmpc::KInst) * (size_t)h->max_batch)) != hipSuccess ||
-      (e = hipMalloc(&rows, sizeof(double) * CMPC_INST_WORDS * (size_t)h->max_batch)) != hipSuccess ||
-      (e = hipMalloc(&bad, sizeof(int))) != hipSuccess) {
-    if (ent) (void)hipFree(ent);
-    if (rows) (void)hipFree(rows);
+  if ((e = ent.alloc((size_t)h->max_batch)) != hipSuccess ||
+      (e = rows.alloc(CMPC_INST_WORDS * (size_t)h->max_batch)) != hipSuccess ||
+      (e = bad.alloc(1)) != hipSuccess)
     return fail("hipMalloc(instance table)", e);
-  }
-  h->d_inst = ent;
-  h->d_inst_rows = rows;
-  h->d_inst_bad = bad;
+  h->d_inst = std::move(ent);
+  h->d_inst_rows = std::move(rows);
+  h->d_inst_bad = std::move(bad);
   return 0;
 }
 
@@ -273,10 +311,7 @@ extern "C" int cmpc_batch_set_params(cmpc_batch* h, const cmpc_params* prm) {
     return -2;
   }
   h->prm = *prm;
-  h->kp = make_kparams(*prm, h->model);
-  if (h->out_steps > 0 && h->out_steps < prm->horizon) h->kp.out_cols = 12 * h->out_steps;
-  if (!h->refine) h->kp.refine = 0;
-  if (int r = apply_inst(h)) return r;
+  if (int r = rebuild_kparams(h)) return r;
   return ensure_admm_slabs(h);
 }
 
@@ -288,82 +323,71 @@ extern "C" int cmpc_batch_set_model(cmpc_batch* h, const cmpc_model* m) {
     return -2;
   }
   h->model = nm;
-  h->kp.mdl = make_kmodel(nm);
-  return apply_inst(h);
+  return rebuild_kparams(h);
 }
 
-extern "C" int cmpc_batch_set_instance_params(cmpc_batch* h, const double* d_inst, int count) {
+// What the two per-instance tables differ in, a row each; set_table is the one setter of both.
+namespace {
+template <class Row>
+struct Table {
+  const char* name;        // the entry point, for the error texts
+  const char* bad_rows;    // what makes a row bad
+  int cmpc_batch::*count;  // the rows in force
+  const char* check_name;  // check: *d_bad += the number of bad rows
+  hipError_t (*check)(const Row* d_rows, int count, int* d_bad, hipStream_t stream);
+  const char* convert_name;  // convert: the rows into the handle's entries (and snapshot)
+  hipError_t (*convert)(const Row* d_rows, int count, cmpc_batch* h);
+};
+const Table<double> kParamTable = {
+    "cmpc_batch_set_instance_params", "mass, inertia and mu must be finite and positive, f_max finite",
+    &cmpc_batch::inst_count, "launch_inst_check", cmpc::launch_inst_check, "launch_inst_convert",
+    [](const double* d, int n, cmpc_batch* h) {
+      return cmpc::launch_inst_convert(d, n, h->d_inst.get(), h->d_inst_rows.get(), h->stream);
+    }};
+const Table<float> kCostTable = {
+    "cmpc_batch_set_instance_costs", "weights must be finite and >= 0, alpha finite and > 0 with 2 alpha finite",
+    &cmpc_batch::cost_count, "launch_cost_check", cmpc::launch_cost_check, "launch_cost_convert",
+    [](const float* d, int n, cmpc_batch* h) { return cmpc::launch_cost_convert(d, n, h->d_inst.get(), h->stream); }};
+
+// d_rows null clears the table: the handle's shared values again (the buffers stay for the next one)
+template <class Row>
+int set_table(cmpc_batch* h, const Table<Row>& t, const Row* d_rows, int count) {
   if (!h) return -1;
   hipError_t e;
-  if (!d_inst) {  // clear: the shared model, mu and f_max again (the buffers stay for the next table)
-    if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
-    h->inst_count = 0;
-    if (int r = apply_inst(h)) return r;  // (under a cost table: the shared model, mu and f_max into its entries)
-    if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
-    return 0;
-  }
-  if (count < 1 || count > h->max_batch) {
-    g_last_error = "cmpc_batch_set_instance_params: count must be in 1..max_batch";
-    return -1;
-  }
-  if (int r = ensure_inst_buffers(h)) return r;  // first call of either table
   int bad = 0;
-  if ((e = hipMemsetAsync(h->d_inst_bad, 0, sizeof(int), h->stream)) != hipSuccess) return fail("memset", e);
-  if ((e = cmpc::launch_inst_check(d_inst, count, h->d_inst_bad, h->stream)) != hipSuccess)
-    return fail("launch_inst_check", e);
-  if ((e = hipMemcpyAsync(&bad, h->d_inst_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
-    return fail("D2H", e);
+  if (d_rows) {
+    if (count < 1 || count > h->max_batch) {
+      g_last_error = std::string(t.name) + ": count must be in 1..max_batch";
+      return -1;
+    }
+    if (int r = ensure_inst_buffers(h)) return r;  // first call of either table
+    int* d_bad = h->d_inst_bad.get();
+    if ((e = hipMemsetAsync(d_bad, 0, sizeof(int), h->stream)) != hipSuccess) return fail("memset", e);
+    if ((e = t.check(d_rows, count, d_bad, h->stream)) != hipSuccess) return fail(t.check_name, e);
+    if (int r = stream_d2h(h, &bad, d_bad, sizeof(int))) return r;
+  }
   // (also: every earlier call on the handle's stream that reads the table in force is done)
-  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
+  if (int r = stream_sync(h)) return r;
   if (bad != 0) {
-    g_last_error = "cmpc_batch_set_instance_params: " + std::to_string(bad) +
-                   " bad row(s): mass, inertia and mu must be finite and positive, f_max finite";
+    g_last_error = std::string(t.name) + ": " + std::to_string(bad) + " bad row(s): " + t.bad_rows;
     return -2;
   }
-  if ((e = cmpc::launch_inst_convert(d_inst, count, h->d_inst, h->d_inst_rows, h->stream)) != hipSuccess)
-    return fail("launch_inst_convert", e);
-  h->inst_count = count;
-  if (int r = apply_inst(h)) return r;  // (without a cost table: the shared weights and alpha beside the rows)
-  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
-  return 0;
+  if (d_rows && (e = t.convert(d_rows, count, h)) != hipSuccess) return fail(t.convert_name, e);
+  h->*t.count = d_rows ? count : 0;
+  // (with one table in force, the other half of its entries from the handle's shared values)
+  if (int r = apply_inst(h)) return r;
+  return stream_sync(h);
+}
+}  // namespace
+
+extern "C" int cmpc_batch_set_instance_params(cmpc_batch* h, const double* d_inst, int count) {
+  return set_table(h, kParamTable, d_inst, count);
 }
 
 extern "C" int cmpc_batch_instance_count(const cmpc_batch* h) { return h ? h->inst_count : 0; }
 
 extern "C" int cmpc_batch_set_instance_costs(cmpc_batch* h, const float* d_cost, int count) {
-  if (!h) return -1;
-  hipError_t e;
-  if (!d_cost) {  // clear: the shared weights and alpha again (the buffers stay for the next table)
-    if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
-    h->cost_count = 0;
-    if (int r = apply_inst(h)) return r;  // (under a parameter table: the shared cost into its entries)
-    if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
-    return 0;
-  }
-  if (count < 1 || count > h->max_batch) {
-    g_last_error = "cmpc_batch_set_instance_costs: count must be in 1..max_batch";
-    return -1;
-  }
-  if (int r = ensure_inst_buffers(h)) return r;  // first call of either table
-  int bad = 0;
-  if ((e = hipMemsetAsync(h->d_inst_bad, 0, sizeof(int), h->stream)) != hipSuccess) return fail("memset", e);
-  if ((e = cmpc::launch_cost_check(d_cost, count, h->d_inst_bad, h->stream)) != hipSuccess)
-    return fail("launch_cost_check", e);
-  if ((e = hipMemcpyAsync(&bad, h->d_inst_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
-    return fail("D2H", e);
-  // (also: every earlier call on the handle's stream that reads the table in force is done)
-  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
-  if (bad != 0) {
-    g_last_error = "cmpc_batch_set_instance_costs: " + std::to_string(bad) +
-                   " bad row(s): weights must be finite and >= 0, alpha finite and > 0 with 2 alpha finite";
-    return -2;
-  }
-  if ((e = cmpc::launch_cost_convert(d_cost, count, h->d_inst, h->stream)) != hipSuccess)
-    return fail("launch_cost_convert", e);
-  h->cost_count = count;
-  if (int r = apply_inst(h)) return r;  // (without a parameter table: the shared model, mu and f_max beside the rows)
-  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
-  return 0;
+  return set_table(h, kCostTable, d_cost, count);
 }
 
 extern "C" int cmpc_batch_instance_cost_count(const cmpc_batch* h) { return h ? h->cost_count : 0; }
@@ -375,40 +399,42 @@ extern "C" int cmpc_batch_get_model(const cmpc_batch* h, cmpc_model* out) {
 }
 
 extern "C" int cmpc_batch_set_refine(cmpc_batch* h, int on) {
-  if (!h || on < 0 || on > 1) {
-    g_last_error = "cmpc_batch_set_refine: bad arguments";
-    return -1;
-  }
+  if (!h || on < 0 || on > 1) return bad_arguments("cmpc_batch_set_refine");
   h->refine = on;
-  h->kp.refine = (on && h->prm.horizon >= CMPC_REFINE_FROM_N) ? 1 : 0;
-  return 0;
+  return rebuild_kparams(h);
 }
 
 extern "C" int cmpc_batch_set_output_steps(cmpc_batch* h, int steps) {
-  if (!h || steps < 0) {
-    g_last_error = "cmpc_batch_set_output_steps: bad arguments";
-    return -1;
-  }
+  if (!h || steps < 0) return bad_arguments("cmpc_batch_set_output_steps");
   h->out_steps = steps;
-  h->kp.out_cols = 12 * ((steps > 0 && steps < h->prm.horizon) ? steps : h->prm.horizon);
-  return 0;
+  return rebuild_kparams(h);
 }
 
-extern "C" int cmpc_batch_create(cmpc_batch** out, const cmpc_params* prm, int max_batch,
-                                 void* hip_stream) {
-  if (!out || !prm || max_batch < 1) return -1;
-  auto* h = new cmpc_batch();
-  if (int r = cmpc_batch_set_params(h, prm); r != 0) {
-    delete h;
-    return r;
-  }
+// The fork / classified / join events order queues of this one device only: every producer and
+// consumer of the data they guard is a kernel on this GPU, whose dispatch packets carry their own
+// device-scope acquire / release (the per-XCD L2s written back and invalidated at kernel
+// boundaries), and the caller's copies to the host order after the join on its stream. So these
+// events are recorded without the system-scope fence HIP adds by default (an L2 writeback and
+// invalidate per record, five records per solve): config 2 +3 to +4 %, 32768 instances +0.5 to
+// +1 %, config 3 +1 % (profiles/r06_s2/env_ab.log; device scope instead: within noise). The timing
+// events (cmpc_batch_enable_timing) are recorded without it too.
+// CMPC_EVENT_SCOPE (A/B): 0 HIP's default (system scope), 1 device scope (ordering events only),
+// 2 no system fence
+static unsigned event_flags(bool timing) {
+  const int scope = cmpc::diag_knob("CMPC_EVENT_SCOPE", 2);
+  const unsigned fence = scope == 2 ? hipEventDisableSystemFence : 0u;
+  if (timing) return fence;
+  return hipEventDisableTiming | (scope == 1 ? hipEventReleaseToDevice : fence);
+}
+
+// everything a new handle acquires; on a failure cmpc_batch_create destroys what was acquired so far
+static int init_handle(cmpc_batch* h, const cmpc_params* prm, int max_batch, void* hip_stream) {
+  if (int r = cmpc_batch_set_params(h, prm)) return r;
   h->max_batch = max_batch;
-  hipError_t e;
   if (hip_stream) {
     h->stream = (hipStream_t)hip_stream;
   } else {
-    e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) { delete h; return fail("hipStreamCreate", e); }
+    if (int r = checked("hipStreamCreate", hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking))) return r;
     h->own_stream = true;
   }
   // side streams at the highest priority: their few, long class-2 solves are dispatched ahead
@@ -416,49 +442,43 @@ extern "C" int cmpc_batch_create(cmpc_batch** out, const cmpc_params* prm, int m
   int prio_lo = 0, prio_hi = 0;
   (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
   if (cmpc::diag_knob("CMPC_SIDE_PRIORITY", 1) == 0) prio_hi = prio_lo;
-  {
-    std::array<hipStream_t, cmpc::kSideStreams> sides{};
-    e = acquire_sides(sides, prio_hi);
-    if (e != hipSuccess) { cmpc_batch_destroy(h); return fail("side streams", e); }
-    for (int j = 0; j < cmpc::kSideStreams; j++) h->ctx.side[j] = sides[j];
-    h->pooled_sides = true;
-  }
-  // The fork / classified / join events order queues of this one device only: every producer and
-  // consumer of the data they guard is a kernel on this GPU, whose dispatch packets carry their own
-  // device-scope acquire / release (the per-XCD L2s written back and invalidated at kernel
-  // boundaries), and the caller's copies to the host order after the join on its stream. So these
-  // events are recorded without the system-scope fence HIP adds by default (an L2 writeback and
-  // invalidate per record, five records per solve): config 2 +3 to +4 %, 32768 instances +0.5 to
-  // +1 %, config 3 +1 % (profiles/r06_s2/env_ab.log; device scope instead: within noise).
-  // CMPC_EVENT_SCOPE (A/B): 0 HIP's default (system scope), 1 device scope, 2 no system fence
-  const int ev_scope = cmpc::diag_knob("CMPC_EVENT_SCOPE", 2);
-  const unsigned ev_flags = hipEventDisableTiming | (ev_scope == 1 ? hipEventReleaseToDevice
-                                                     : ev_scope == 2 ? hipEventDisableSystemFence : 0u);
-  for (int j = 0; j < cmpc::kSideStreams; j++) {
-    e = hipEventCreateWithFlags(&h->ctx.join[j], ev_flags);
-    if (e != hipSuccess) { cmpc_batch_destroy(h); return fail("side events", e); }
-  }
-  e = hipEventCreateWithFlags(&h->ctx.fork, ev_flags);
+  std::array<hipStream_t, cmpc::kSideStreams> sides{};
+  if (int r = checked("side streams", acquire_sides(sides, prio_hi))) return r;
+  for (int j = 0; j < cmpc::kSideStreams; j++) h->ctx.side[j] = sides[j];
+  h->pooled_sides = true;
+  const unsigned ev_flags = event_flags(false);
+  for (int j = 0; j < cmpc::kSideStreams; j++)
+    if (int r = checked("side events", hipEventCreateWithFlags(&h->ctx.join[j], ev_flags))) return r;
+  hipError_t e = hipEventCreateWithFlags(&h->ctx.fork, ev_flags);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ctx.classified, ev_flags);
-  if (e != hipSuccess) { cmpc_batch_destroy(h); return fail("fork event", e); }
+  if (e != hipSuccess) return fail("fork event", e);
   // the class-count hint (cmpc_launch.hip): pinned, mapped, zero (no hint) until a classify pass
   // copies a finished solve's header into it
-  e = hipHostMalloc(reinterpret_cast<void**>(&h->ctx.h_hint), sizeof(int) * cmpc::kHdr, hipHostMallocMapped);
+  e = h->h_hint.alloc(cmpc::kHdr, hipHostMallocMapped);
   if (e == hipSuccess) {
+    h->ctx.h_hint = h->h_hint.get();
     std::memset(h->ctx.h_hint, 0, sizeof(int) * cmpc::kHdr);
     e = hipHostGetDevicePointer(reinterpret_cast<void**>(&h->ctx.d_hint), h->ctx.h_hint, 0);
   }
-  if (e != hipSuccess) { cmpc_batch_destroy(h); return fail("hint buffer", e); }
-  e = hipMalloc(&h->d_work, sizeof(int) * cmpc::work_ints(max_batch));
-  if (e == hipSuccess) e = hipMemset(h->d_work, 0, sizeof(int) * 2 * cmpc::kHdr);  // both list headers
-  if (e != hipSuccess) { cmpc_batch_destroy(h); return fail("hipMalloc(work)", e); }
-  {
-    float taps[cmpc::kGaussTaps];
-    gauss_kernel(7.0f, cmpc::kGaussR7, taps);
-    gauss_kernel(27.0f, cmpc::kGaussR27, taps + 2 * cmpc::kGaussR7 + 1);
-    e = hipMalloc(&h->d_gauss, sizeof(taps));
-    if (e == hipSuccess) e = hipMemcpy(h->d_gauss, taps, sizeof(taps), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { cmpc_batch_destroy(h); return fail("gauss taps", e); }
+  if (e != hipSuccess) return fail("hint buffer", e);
+  e = h->d_work.alloc(cmpc::work_ints(max_batch));
+  if (e == hipSuccess) e = hipMemset(h->d_work.get(), 0, sizeof(int) * 2 * cmpc::kHdr);  // both list headers
+  if (e != hipSuccess) return fail("hipMalloc(work)", e);
+  float taps[cmpc::kGaussTaps];
+  gauss_kernel(7.0f, cmpc::kGaussR7, taps);
+  gauss_kernel(27.0f, cmpc::kGaussR27, taps + 2 * cmpc::kGaussR7 + 1);
+  e = h->d_gauss.alloc(cmpc::kGaussTaps);
+  if (e == hipSuccess) e = hipMemcpy(h->d_gauss.get(), taps, sizeof(taps), hipMemcpyHostToDevice);
+  return checked("gauss taps", e);
+}
+
+extern "C" int cmpc_batch_create(cmpc_batch** out, const cmpc_params* prm, int max_batch,
+                                 void* hip_stream) {
+  if (!out || !prm || max_batch < 1) return -1;
+  auto* h = new cmpc_batch();
+  if (int r = init_handle(h, prm, max_batch, hip_stream)) {
+    cmpc_batch_destroy(h);  // (leaves cmpc_last_error as the failed step set it)
+    return r;
   }
   *out = h;
   return 0;
@@ -466,14 +486,17 @@ extern "C" int cmpc_batch_create(cmpc_batch** out, const cmpc_params* prm, int m
 
 static void free_staging(cmpc_batch* h);
 
+// The order is part of the contract: the buffers first (here, not by the handle's destructor), the
+// side streams idle and back in the pool, the events, the own stream idle, then the hint buffer its
+// kernels write, then the stream itself.
 extern "C" void cmpc_batch_destroy(cmpc_batch* h) {
   if (!h) return;
-  if (h->d_work) (void)hipFree(h->d_work);
-  if (h->d_gauss) (void)hipFree(h->d_gauss);
-  if (h->d_admm_slabs) (void)hipFree(h->d_admm_slabs);
-  if (h->d_inst) (void)hipFree(h->d_inst);
-  if (h->d_inst_rows) (void)hipFree(h->d_inst_rows);
-  if (h->d_inst_bad) (void)hipFree(h->d_inst_bad);
+  h->d_work.reset();
+  h->d_gauss.reset();
+  h->d_admm_slabs.reset();
+  h->d_inst.reset();
+  h->d_inst_rows.reset();
+  h->d_inst_bad.reset();
   free_staging(h);
   for (auto e : h->ev) (void)hipEventDestroy(e);
   if (h->pooled_sides) {
@@ -490,118 +513,83 @@ extern "C" void cmpc_batch_destroy(cmpc_batch* h) {
   if (h->ctx.fork) (void)hipEventDestroy(h->ctx.fork);
   if (h->ctx.classified) (void)hipEventDestroy(h->ctx.classified);
   if (h->own_stream && h->stream) (void)hipStreamSynchronize(h->stream);
-  if (h->ctx.h_hint) (void)hipHostFree(h->ctx.h_hint);  // (the classify kernels writing it are done)
+  h->h_hint.reset();  // (the classify kernels writing it are done)
+  h->ctx.h_hint = nullptr;
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
   delete h;
 }
 
 extern "C" void* cmpc_batch_stream(cmpc_batch* h) { return h ? (void*)h->stream : nullptr; }
 
-extern "C" int cmpc_batch_solve(cmpc_batch* h, const float* d_records, int batch, float* d_forces,
-                                uint8_t* d_status, int32_t* d_iters) {
-  if (!h || !batch_ok(h, batch) || (!d_records && batch) || (!d_forces && batch) ||
-      (!d_status && batch)) {
-    g_last_error = "cmpc_batch_solve: bad arguments";
-    return -1;
-  }
-  hipEvent_t* ev = nullptr;
+// the events of this solve's launches, where per-launch timing is on and this solve is due for it
+static hipEvent_t* next_timing_events(cmpc_batch* h) {
   if (h->ev_steps > 0 && h->ev_next < h->ev_steps && h->ev_solves++ % h->ev_every == 0)
-    ev = &h->ev[3 * h->ev_next++];
+    return &h->ev[3 * h->ev_next++];
+  return nullptr;
+}
+
+// The masked entry points are the bodies of their plain forms too: the plain form is the masked one
+// with a null mask, and says so in its error text.
+extern "C" int cmpc_batch_solve_due(cmpc_batch* h, const float* d_records, const uint8_t* d_due, int batch,
+                                    float* d_forces, uint8_t* d_status, int32_t* d_iters) {
+  if (!h || !batch_ok(h, batch) || (!d_records && batch) || (!d_forces && batch) || (!d_status && batch))
+    return bad_arguments(d_due ? "cmpc_batch_solve_due" : "cmpc_batch_solve");
   // (A HIP graph of this launch sequence, replayed while the arguments repeat, measured config 3
   // 41.8 M -> 32.5 M and config 2 14.7 M -> 9.8 M QP/s: the replay lost the overlap of class 1
   // with the side-stream classes, profiles/r04_ab/r04_m*. Direct launches only.)
-  const hipError_t e = cmpc::launch_solve(d_records, batch, h->kp, d_forces, d_status, d_iters, h->d_work,
-                                          h->max_batch, h->stream, h->ctx, ev);
-  if (e != hipSuccess) return fail("launch_solve", e);
-  return 0;
+  return checked("launch_solve",
+                 cmpc::launch_solve(d_records, batch, h->kp, d_forces, d_status, d_iters, h->d_work.get(), h->max_batch,
+                                    h->stream, h->ctx, next_timing_events(h), d_due));
 }
 
-extern "C" int cmpc_batch_solve_due(cmpc_batch* h, const float* d_records, const uint8_t* d_due, int batch,
-                                    float* d_forces, uint8_t* d_status, int32_t* d_iters) {
-  if (!d_due) return cmpc_batch_solve(h, d_records, batch, d_forces, d_status, d_iters);
-  if (!h || !batch_ok(h, batch) || (!d_records && batch) || (!d_forces && batch) ||
-      (!d_status && batch)) {
-    g_last_error = "cmpc_batch_solve_due: bad arguments";
-    return -1;
-  }
-  hipEvent_t* ev = nullptr;
-  if (h->ev_steps > 0 && h->ev_next < h->ev_steps && h->ev_solves++ % h->ev_every == 0)
-    ev = &h->ev[3 * h->ev_next++];
-  const hipError_t e = cmpc::launch_solve(d_records, batch, h->kp, d_forces, d_status, d_iters, h->d_work,
-                                          h->max_batch, h->stream, h->ctx, ev, d_due);
-  if (e != hipSuccess) return fail("launch_solve", e);
-  return 0;
+extern "C" int cmpc_batch_solve(cmpc_batch* h, const float* d_records, int batch, float* d_forces,
+                                uint8_t* d_status, int32_t* d_iters) {
+  return cmpc_batch_solve_due(h, d_records, nullptr, batch, d_forces, d_status, d_iters);
 }
 
 extern "C" int cmpc_batch_estimate_due(cmpc_batch* h, float* d_est, const float* d_logs,
                                        const float* d_fext3, const float* d_time, float sim_time,
                                        float* d_records, float* d_fext6, const uint8_t* d_due, int batch) {
-  if (!d_due) return cmpc_batch_estimate(h, d_est, d_logs, d_fext3, d_time, sim_time, d_records, d_fext6, batch);
-  if (!h || !batch_ok(h, batch) || (batch && (!d_est || !d_records)) ||
-      (batch && !d_logs && !d_fext3)) {
-    g_last_error = "cmpc_batch_estimate_due: bad arguments";
-    return -1;
-  }
-  hipError_t e = cmpc::launch_estimate(d_est, d_logs, d_fext3, d_time, sim_time, d_records, h->kp.rec_words,
-                                       d_fext6, h->d_gauss, batch, h->stream, h->kp.mdl, nullptr, d_due,
-                                       h->kp.inst);
-  if (e != hipSuccess) return fail("launch_estimate", e);
-  return 0;
+  if (!h || !batch_ok(h, batch) || (batch && (!d_est || !d_records)) || (batch && !d_logs && !d_fext3))
+    return bad_arguments(d_due ? "cmpc_batch_estimate_due" : "cmpc_batch_estimate");
+  return checked("launch_estimate",
+                 cmpc::launch_estimate(d_est, d_logs, d_fext3, d_time, sim_time, d_records, h->kp.rec_words, d_fext6,
+                                       h->d_gauss.get(), batch, h->stream, h->kp.mdl, nullptr, d_due, h->kp.inst));
 }
 
 extern "C" int cmpc_batch_estimate(cmpc_batch* h, float* d_est, const float* d_logs,
                                    const float* d_fext3, const float* d_time, float sim_time,
                                    float* d_records, float* d_fext6, int batch) {
-  if (!h || !batch_ok(h, batch) || (batch && (!d_est || !d_records)) ||
-      (batch && !d_logs && !d_fext3)) {
-    g_last_error = "cmpc_batch_estimate: bad arguments";
-    return -1;
-  }
-  hipError_t e = cmpc::launch_estimate(d_est, d_logs, d_fext3, d_time, sim_time, d_records,
-                                       h->kp.rec_words, d_fext6, h->d_gauss, batch, h->stream, h->kp.mdl,
-                                       nullptr, nullptr, h->kp.inst);
-  if (e != hipSuccess) return fail("launch_estimate", e);
-  return 0;
+  return cmpc_batch_estimate_due(h, d_est, d_logs, d_fext3, d_time, sim_time, d_records, d_fext6, nullptr, batch);
 }
 
 extern "C" int cmpc_batch_assemble(cmpc_batch* h, float* d_loco, const cmpc_loco_params* lp,
                                    float* d_records, uint8_t* d_due, int batch) {
   if (!h || !lp || batch < 0 || batch > h->max_batch ||
       (batch && (!d_loco || !d_records || !d_due)) || !(lp->dt > 0.f) ||
-      lp->iters_between_mpc < 1) {
-    g_last_error = "cmpc_batch_assemble: bad arguments";
-    return -1;
-  }
+      lp->iters_between_mpc < 1)
+    return bad_arguments("cmpc_batch_assemble");
   cmpc::LocoParams kp{lp->dt,        lp->iters_between_mpc, lp->x_drag_gain,  h->kp.N,
                       h->kp.rec_words, lp->hip_x,            lp->hip_y,        lp->abad_link,
                       lp->swing_height, lp->bonus_swing,     h->kp.out_cols};
-  hipError_t e = cmpc::launch_assemble(d_loco, kp, d_records, d_due, batch, h->stream);
-  if (e != hipSuccess) return fail("launch_assemble", e);
-  return 0;
+  return checked("launch_assemble", cmpc::launch_assemble(d_loco, kp, d_records, d_due, batch, h->stream));
 }
 
 extern "C" int cmpc_batch_expand(cmpc_batch* h, const float* d_compact, float* d_records, int batch) {
-  if (!h || batch < 0 || batch > h->max_batch || (batch && (!d_compact || !d_records))) {
-    g_last_error = "cmpc_batch_expand: bad arguments";
-    return -1;
-  }
-  hipError_t e = cmpc::launch_expand(d_compact, d_records, batch, h->kp.N, h->kp.rec_words, h->kp.dt, h->stream);
-  if (e != hipSuccess) return fail("launch_expand", e);
-  return 0;
+  if (!h || batch < 0 || batch > h->max_batch || (batch && (!d_compact || !d_records)))
+    return bad_arguments("cmpc_batch_expand");
+  return checked("launch_expand",
+                 cmpc::launch_expand(d_compact, d_records, batch, h->kp.N, h->kp.rec_words, h->kp.dt, h->stream));
 }
 
 extern "C" int cmpc_batch_rollout(cmpc_batch* h, float* d_loco, const float* d_records,
                                   const float* d_forces, const float* d_xi6, const uint8_t* d_due,
                                   int batch) {
-  if (!h || !batch_ok(h, batch) || (batch && (!d_loco || !d_records || !d_forces))) {
-    g_last_error = "cmpc_batch_rollout: bad arguments";
-    return -1;
-  }
+  if (!h || !batch_ok(h, batch) || (batch && (!d_loco || !d_records || !d_forces)))
+    return bad_arguments("cmpc_batch_rollout");
   cmpc::LocoParams kp{h->kp.dt, 1, 0.f, h->kp.N, h->kp.rec_words, 0.f, 0.f, 0.f, 0.f, 0.f, h->kp.out_cols};
-  hipError_t e = cmpc::launch_rollout(d_loco, d_records, d_forces, d_xi6, d_due, kp, h->kp.dt,
-                                      h->kp.mdl, batch, h->stream, h->kp.inst);
-  if (e != hipSuccess) return fail("launch_rollout", e);
-  return 0;
+  return checked("launch_rollout", cmpc::launch_rollout(d_loco, d_records, d_forces, d_xi6, d_due, kp, h->kp.dt,
+                                                        h->kp.mdl, batch, h->stream, h->kp.inst));
 }
 
 extern "C" int cmpc_batch_enable_timing(cmpc_batch* h, int steps) {
@@ -614,8 +602,7 @@ extern "C" int cmpc_batch_enable_timing_every(cmpc_batch* h, int steps, int ever
   h->ev_solves = 0;
   for (auto e : h->ev) (void)hipEventDestroy(e);
   h->ev.assign(3 * (size_t)steps, nullptr);
-  // recorded without the system-scope fence too (timing only; CMPC_EVENT_SCOPE as above)
-  const unsigned tflags = cmpc::diag_knob("CMPC_EVENT_SCOPE", 2) == 2 ? hipEventDisableSystemFence : 0u;
+  const unsigned tflags = event_flags(true);
   for (auto& e : h->ev)
     if (hipError_t r = hipEventCreateWithFlags(&e, tflags); r != hipSuccess) return fail("hipEventCreate", r);
   h->ev_steps = steps;
@@ -626,8 +613,7 @@ extern "C" int cmpc_batch_enable_timing_every(cmpc_batch* h, int steps, int ever
 extern "C" int cmpc_batch_read_timing(cmpc_batch* h, float* ms, int* steps_recorded,
                                       int* class1_overflow) {
   if (!h) return -1;
-  hipError_t e = hipStreamSynchronize(h->stream);
-  if (e != hipSuccess) return fail("sync", e);
+  if (int r = stream_sync(h)) return r;
   for (int i = 0; i < h->ev_next; i++) {
     float a = 0.f, b = 0.f;
     (void)hipEventElapsedTime(&a, h->ev[3 * i], h->ev[3 * i + 1]);
@@ -639,7 +625,7 @@ extern "C" int cmpc_batch_read_timing(cmpc_batch* h, float* ms, int* steps_recor
   if (steps_recorded) *steps_recorded = h->ev_next;
   if (class1_overflow) {
     int c = 0;
-    e = hipMemcpy(&c, h->d_work + h->ctx.last_hdr * cmpc::kHdr, sizeof(int), hipMemcpyDeviceToHost);
+    const hipError_t e = hipMemcpy(&c, h->d_work.get() + h->ctx.last_hdr * cmpc::kHdr, sizeof(int), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail("D2H", e);
     *class1_overflow = c;
   }
@@ -647,57 +633,46 @@ extern "C" int cmpc_batch_read_timing(cmpc_batch* h, float* ms, int* steps_recor
   return 0;
 }
 
+static int condense_device(cmpc_batch* h, const float* d_records, int batch, float* d_H, float* d_g, bool rows) {
+  if (!h || !batch_ok(h, batch)) return -1;
+  return checked("launch_condense", cmpc::launch_condense(d_records, batch, h->kp, d_H, d_g, rows, h->stream));
+}
+
 extern "C" int cmpc_batch_condense(cmpc_batch* h, const float* d_records, int batch, float* d_H,
                                    float* d_g) {
-  if (!h || !batch_ok(h, batch)) return -1;
-  hipError_t e = cmpc::launch_condense(d_records, batch, h->kp, d_H, d_g, false, h->stream);
-  if (e != hipSuccess) return fail("launch_condense", e);
-  return 0;
+  return condense_device(h, d_records, batch, d_H, d_g, false);
 }
 
 extern "C" int cmpc_batch_condense_rows(cmpc_batch* h, const float* d_records, int batch, float* d_H,
                                         float* d_g) {
-  if (!h || !batch_ok(h, batch)) return -1;
-  hipError_t e = cmpc::launch_condense(d_records, batch, h->kp, d_H, d_g, true, h->stream);
-  if (e != hipSuccess) return fail("launch_condense", e);
-  return 0;
+  return condense_device(h, d_records, batch, d_H, d_g, true);
 }
 
 extern "C" int cmpc_batch_admm(cmpc_batch* h, const float* d_records, const float* d_H,
                                const float* d_g, int batch, const cmpc_admm_settings* s,
                                float* d_forces, uint8_t* d_status, int32_t* d_iters) {
   if (!h || !s || !batch_ok(h, batch) ||
-      (batch && (!d_records || !d_H || !d_g || !d_forces || !d_status))) {
-    g_last_error = "cmpc_batch_admm: bad arguments";
-    return -1;
-  }
+      (batch && (!d_records || !d_H || !d_g || !d_forces || !d_status)))
+    return bad_arguments("cmpc_batch_admm");
   if (!h->admm_used) {
     h->admm_used = true;
     if (int r = ensure_admm_slabs(h)) { h->admm_used = false; return r; }
   }
-  hipError_t e = cmpc::launch_admm(d_records, d_H, d_g, batch, h->kp, *s, d_forces, d_status,
-                                   d_iters, h->d_admm_slabs, h->admm_nslabs, h->stream);
-  if (e != hipSuccess) return fail("launch_admm", e);
-  return 0;
+  return checked("launch_admm", cmpc::launch_admm(d_records, d_H, d_g, batch, h->kp, *s, d_forces, d_status,
+                                                  d_iters, h->d_admm_slabs.get(), h->admm_nslabs, h->stream));
 }
 
 static void free_staging(cmpc_batch* h) {
-  if (h->d_rec) (void)hipFree(h->d_rec);
-  if (h->d_forces) (void)hipFree(h->d_forces);
-  if (h->d_status) (void)hipFree(h->d_status);
-  if (h->d_iters) (void)hipFree(h->d_iters);
-  if (h->d_admm_H) (void)hipFree(h->d_admm_H);
-  if (h->d_one) (void)hipFree(h->d_one);
-  if (h->d_single_out) (void)hipFree(h->d_single_out);
-  if (h->h_pin) (void)hipHostFree(h->h_pin);
-  if (h->d_xpred) (void)hipFree(h->d_xpred);
-  if (h->d_cert) (void)hipFree(h->d_cert);
-  h->d_xpred = nullptr;
-  h->d_cert = nullptr;
-  h->d_rec = h->d_forces = h->d_admm_H = h->d_single_out = h->h_pin = nullptr;
-  h->d_status = nullptr;
-  h->d_iters = nullptr;
-  h->d_one = nullptr;
+  h->d_rec.reset();
+  h->d_forces.reset();
+  h->d_status.reset();
+  h->d_iters.reset();
+  h->d_admm_H.reset();
+  h->d_one.reset();
+  h->d_single_out.reset();
+  h->h_pin.reset();
+  h->d_xpred.reset();
+  h->d_cert.reset();
   h->staged = false;
 }
 
@@ -705,23 +680,22 @@ static void free_staging(cmpc_batch* h) {
 // allocation frees what was allocated, so a later call retries instead of using null buffers)
 static int ensure_staging(cmpc_batch* h) {
   if (h->staged) return 0;
-  const size_t words = (size_t)CMPC_REC_WORDS(CMPC_MAX_HORIZON) * h->max_batch;
-  const size_t nv = 12 * (size_t)CMPC_MAX_HORIZON;  // qH / qg of one instance (single ADMM path)
+  const size_t B = (size_t)h->max_batch;
+  const size_t nv = Stage::kForcesMax;  // qH / qg of one instance (single ADMM path)
   const int one[2] = {1, 0};
   hipError_t e;
   const char* what = "hipMalloc";
-  // d_rec: 4 words past the last record for the single-instance ABI's (f_ext[3], simulation_time)
-  if ((e = hipMalloc(&h->d_rec, (words + 4) * sizeof(float))) == hipSuccess &&
-      (e = hipMalloc(&h->d_forces, (size_t)12 * CMPC_MAX_HORIZON * h->max_batch * sizeof(float))) == hipSuccess &&
-      (e = hipMalloc(&h->d_status, (size_t)h->max_batch)) == hipSuccess &&
-      (e = hipMalloc(&h->d_iters, sizeof(int32_t) * h->max_batch)) == hipSuccess &&
-      (e = hipMalloc(&h->d_admm_H, (nv * nv + nv) * sizeof(float))) == hipSuccess &&
-      (e = hipMalloc(&h->d_one, sizeof(one))) == hipSuccess &&
-      (e = hipMalloc(&h->d_single_out, (12 * CMPC_MAX_HORIZON + 4) * sizeof(float))) == hipSuccess &&
-      (what = "hipHostMalloc",
-       e = hipHostMalloc(reinterpret_cast<void**>(&h->h_pin),
-                         (CMPC_REC_WORDS(CMPC_MAX_HORIZON) + 4 + 12 * CMPC_MAX_HORIZON + 4) * sizeof(float))) == hipSuccess &&
-      (what = "H2D", e = hipMemcpy(h->d_one, one, sizeof(one), hipMemcpyHostToDevice)) == hipSuccess) {
+  // d_rec: kPad words past the last record, so the single-instance round trip's words behind its
+  // one record fit whatever max_batch is
+  if ((e = h->d_rec.alloc(Stage::kRecMax * B + Stage::kPad)) == hipSuccess &&
+      (e = h->d_forces.alloc(Stage::kForcesMax * B)) == hipSuccess &&
+      (e = h->d_status.alloc(B)) == hipSuccess &&
+      (e = h->d_iters.alloc(B)) == hipSuccess &&
+      (e = h->d_admm_H.alloc(nv * nv + nv)) == hipSuccess &&
+      (e = h->d_one.alloc(2)) == hipSuccess &&
+      (e = h->d_single_out.alloc(Stage::kOutWords)) == hipSuccess &&
+      (what = "hipHostMalloc", e = h->h_pin.alloc(Stage::kPinWords)) == hipSuccess &&
+      (what = "H2D", e = hipMemcpy(h->d_one.get(), one, sizeof(one), hipMemcpyHostToDevice)) == hipSuccess) {
     h->staged = true;
     return 0;
   }
@@ -741,53 +715,65 @@ static int host_reduced_size(const float* rec, int N, float f_max) {
   return 3 * nfs;
 }
 
+// The record of one instance, and `in_extra` words behind it (0, or 2: the reference surface's
+// f_ext[3] and simulation_time), through pinned memory to h->d_rec in one H2D. With d_est, the
+// estimator step on those two words follows: it writes f_est(3) and the use-f_est flag into the
+// device record, and f_est(3) behind the status word of d_single_out.
+static int single_upload(cmpc_batch* h, const float* rec, const float* extra, int in_extra, float* d_est) {
+  const int N = h->prm.horizon;
+  const size_t rw = (size_t)CMPC_REC_WORDS(N);
+  float* pin_rec = h->h_pin.get();
+  float* d_rec = h->d_rec.get();
+  std::memcpy(pin_rec, rec, rw * sizeof(float));
+  if (in_extra) std::memcpy(pin_rec + rw, extra, in_extra * sizeof(float));
+  if (int r = stream_h2d(h, d_rec, pin_rec, (rw + in_extra) * sizeof(float))) return r;
+  if (!d_est) return 0;
+  return checked("launch_estimate",
+                 cmpc::launch_estimate(d_est, nullptr, d_rec + rw, d_rec + rw + 1, 0.f, d_rec, (int)rw, nullptr,
+                                       h->d_gauss.get(), 1, h->stream, h->kp.mdl,
+                                       h->d_single_out.get() + Stage::status_word(N) + 1));
+}
+
+// One instance from host memory through the kernel of its size class: the round trip of
+// cmpc_batch_solve_host's batch of one and of the reference surface's qpOASES-equivalent solve.
+// single_upload, launch_single, one D2H of the forces, the status word and `out_extra` words behind
+// it (0, or 1: f_est(3)), sync. The result stays in the pinned out area, which is returned through
+// `out`, for the caller to unpack.
 // The tail classes hand an instance whose active set outgrows 64 positions to the 80-column wide
-// class (cmpc_tail.hip); on the single-instance path that shows as the status byte kHandoffStatus:
-// re-launch the record (already on the device) in the wide class and read the result again
-static int single_handoff(cmpc_batch* h, int n, float* pin_out, int N, int32_t* iters = nullptr) {
-  uint8_t st = 0;
-  std::memcpy(&st, pin_out + 12 * N, 1);
-  if (st != cmpc::kHandoffStatus) return 0;
-  float* d_out = h->d_single_out;
-  uint8_t* d_st = reinterpret_cast<uint8_t*>(d_out + 12 * N);
-  hipError_t e;
-  if ((e = cmpc::launch_single(h->d_rec, n, h->kp, d_out, d_st, h->d_iters, h->d_one, h->stream, false)) !=
-      hipSuccess)
-    return fail("launch_single", e);
-  if ((e = hipMemcpyAsync(pin_out, d_out, (12 * N + 1) * sizeof(float), hipMemcpyDeviceToHost, h->stream)) !=
-      hipSuccess)
-    return fail("D2H", e);
-  if (iters && (e = hipMemcpyAsync(iters, h->d_iters, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
-    return fail("D2H", e);
-  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
+// class (cmpc_tail.hip), which shows here as the status byte kHandoffStatus: the record, already on
+// the device, is then launched once more in the wide class and read again (the words behind the
+// status word stay from the first read).
+static int single_round_trip(cmpc_batch* h, const float* rec, const float* extra, int in_extra, int out_extra,
+                             float* d_est, int32_t* iters, const float** out) {
+  if (int r = single_upload(h, rec, extra, in_extra, d_est)) return r;
+  const int N = h->prm.horizon;
+  const int n = host_reduced_size(rec, N, h->prm.f_max);
+  float* pin_out = h->h_pin.get() + Stage::kPinOut;
+  float* d_out = h->d_single_out.get();
+  uint8_t* d_st = reinterpret_cast<uint8_t*>(d_out + Stage::status_word(N));
+  for (const bool first : {true, false}) {
+    const hipError_t e = cmpc::launch_single(h->d_rec.get(), n, h->kp, d_out, d_st, h->d_iters.get(), h->d_one.get(),
+                                             h->stream, /*allow_tail=*/first);
+    if (e != hipSuccess) return fail("launch_single", e);
+    if (int r = stream_d2h(h, pin_out, d_out, Stage::out_words(N, first ? out_extra : 0) * sizeof(float))) return r;
+    if (iters)
+      if (int r = stream_d2h(h, iters, h->d_iters.get(), sizeof(int32_t))) return r;
+    if (int r = stream_sync(h)) return r;
+    uint8_t st = 0;
+    std::memcpy(&st, pin_out + Stage::status_word(N), 1);
+    if (st != cmpc::kHandoffStatus) break;
+  }
+  *out = pin_out;
   return 0;
 }
 
 // batch == 1 from host memory: one kernel of the instance's class, pinned copies, one D2H
 static int solve_single_host(cmpc_batch* h, const float* record, float* forces, uint8_t* status,
                              int32_t* iters) {
-  const int N = h->prm.horizon;
-  const size_t rw = (size_t)CMPC_REC_WORDS(N);
-  const int n = host_reduced_size(record, N, h->prm.f_max);
-  float* pin_rec = h->h_pin;
-  float* pin_out = h->h_pin + CMPC_REC_WORDS(CMPC_MAX_HORIZON) + 4;
-  std::memcpy(pin_rec, record, rw * sizeof(float));
-  float* d_out = h->d_single_out;
-  uint8_t* d_st = reinterpret_cast<uint8_t*>(d_out + 12 * N);
-  hipError_t e;
-  if ((e = hipMemcpyAsync(h->d_rec, pin_rec, rw * sizeof(float), hipMemcpyHostToDevice, h->stream)) != hipSuccess)
-    return fail("H2D", e);
-  if ((e = cmpc::launch_single(h->d_rec, n, h->kp, d_out, d_st, h->d_iters, h->d_one, h->stream)) !=
-      hipSuccess)
-    return fail("launch_single", e);
-  if ((e = hipMemcpyAsync(pin_out, d_out, (12 * N + 1) * sizeof(float), hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
-    return fail("D2H", e);
-  if (iters && (e = hipMemcpyAsync(iters, h->d_iters, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
-    return fail("D2H", e);
-  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
-  if (int r = single_handoff(h, n, pin_out, N, iters)) return r;
-  std::memcpy(forces, pin_out, h->kp.out_cols * sizeof(float));
-  if (status) std::memcpy(status, pin_out + 12 * N, 1);
+  const float* out = nullptr;
+  if (int r = single_round_trip(h, record, nullptr, 0, 0, nullptr, iters, &out)) return r;
+  std::memcpy(forces, out, h->kp.out_cols * sizeof(float));
+  if (status) std::memcpy(status, out + Stage::status_word(h->prm.horizon), 1);
   return 0;
 }
 
@@ -802,81 +788,66 @@ extern "C" int cmpc_batch_solve_host(cmpc_batch* h, const float* records, int ba
   // is on (it brackets the batched launch sequence)
   // (with a per-instance table the batched sequence: its classify pass reads the row's f_max)
   if (batch == 1 && h->ev_steps == 0 && !h->kp.inst) return solve_single_host(h, records, forces, status, iters);
-  hipError_t e;
-  if ((e = hipMemcpyAsync(h->d_rec, records, rw * batch * sizeof(float), hipMemcpyHostToDevice, h->stream)) != hipSuccess)
-    return fail("H2D", e);
-  if (int r = cmpc_batch_solve(h, h->d_rec, batch, h->d_forces, h->d_status, h->d_iters)) return r;
-  if ((e = hipMemcpyAsync(forces, h->d_forces, sizeof(float) * h->kp.out_cols * batch, hipMemcpyDeviceToHost,
-                          h->stream)) != hipSuccess)
-    return fail("D2H", e);
-  if (status && (e = hipMemcpyAsync(status, h->d_status, batch, hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
-    return fail("D2H", e);
-  if (iters && (e = hipMemcpyAsync(iters, h->d_iters, sizeof(int32_t) * batch, hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
-    return fail("D2H", e);
-  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
+  if (int r = stream_h2d(h, h->d_rec.get(), records, rw * batch * sizeof(float))) return r;
+  if (int r = cmpc_batch_solve(h, h->d_rec.get(), batch, h->d_forces.get(), h->d_status.get(), h->d_iters.get()))
+    return r;
+  if (int r = stream_d2h(h, forces, h->d_forces.get(), sizeof(float) * h->kp.out_cols * batch)) return r;
+  if (status)
+    if (int r = stream_d2h(h, status, h->d_status.get(), batch)) return r;
+  if (iters)
+    if (int r = stream_d2h(h, iters, h->d_iters.get(), sizeof(int32_t) * batch)) return r;
+  return stream_sync(h);
+}
+
+// what both evaluate entry points ask of their arguments; `partial`: the entry point's own end of
+// the text for a handle that keeps fewer than N output steps
+static int evaluate_check(const char* who, const cmpc_batch* h, int batch, const void* records, const void* forces,
+                          const void* xpred, const void* cert, const char* partial) {
+  if (!h || !batch_ok(h, batch) || (batch && (!records || !forces))) return bad_arguments(who);
+  if (!xpred && !cert) {
+    g_last_error = std::string(who) + ": both outputs are NULL";
+    return -1;
+  }
+  if (h->kp.out_cols != 12 * h->prm.horizon) {
+    g_last_error = std::string(who) + ": the handle keeps fewer than N output steps" + partial;
+    return -3;
+  }
   return 0;
 }
 
 extern "C" int cmpc_batch_evaluate(cmpc_batch* h, const float* d_records, const float* d_forces, int batch,
                                    float* d_xpred, double* d_cert) {
-  if (!h || !batch_ok(h, batch) || (batch && (!d_records || !d_forces))) {
-    g_last_error = "cmpc_batch_evaluate: bad arguments";
-    return -1;
-  }
-  if (!d_xpred && !d_cert) {
-    g_last_error = "cmpc_batch_evaluate: both outputs are NULL";
-    return -1;
-  }
-  if (h->kp.out_cols != 12 * h->prm.horizon) {
-    g_last_error = "cmpc_batch_evaluate: the handle keeps fewer than N output steps, its forces are not a full solution";
-    return -3;
-  }
-  const hipError_t e = cmpc::launch_evaluate(d_records, d_forces, batch, h->kp, (double)h->prm.alpha,
-                                             h->model.inertia, d_xpred, d_cert, h->stream, h->d_inst_rows);
-  if (e != hipSuccess) return fail("launch_evaluate", e);
-  return 0;
+  if (int r = evaluate_check("cmpc_batch_evaluate", h, batch, d_records, d_forces, d_xpred, d_cert,
+                             ", its forces are not a full solution"))
+    return r;
+  return checked("launch_evaluate",
+                 cmpc::launch_evaluate(d_records, d_forces, batch, h->kp, (double)h->prm.alpha, h->model.inertia,
+                                       d_xpred, d_cert, h->stream, h->d_inst_rows.get()));
 }
 
 extern "C" int cmpc_batch_evaluate_host(cmpc_batch* h, const float* records, const float* forces, int batch,
                                         float* xpred, double* cert) {
-  if (!h || !batch_ok(h, batch) || (batch && (!records || !forces))) {
-    g_last_error = "cmpc_batch_evaluate_host: bad arguments";
-    return -1;
-  }
-  if (!xpred && !cert) {
-    g_last_error = "cmpc_batch_evaluate_host: both outputs are NULL";
-    return -1;
-  }
-  if (h->kp.out_cols != 12 * h->prm.horizon) {
-    g_last_error = "cmpc_batch_evaluate_host: the handle keeps fewer than N output steps";
-    return -3;
-  }
+  if (int r = evaluate_check("cmpc_batch_evaluate_host", h, batch, records, forces, xpred, cert, "")) return r;
   if (batch == 0) return 0;
   if (int r = ensure_staging(h)) return r;
   hipError_t e;
-  if (!h->d_xpred && (e = hipMalloc(&h->d_xpred, (size_t)12 * CMPC_MAX_HORIZON * h->max_batch * sizeof(float))) != hipSuccess) {
-    h->d_xpred = nullptr;
-    return fail("hipMalloc(x_pred)", e);
-  }
-  if (!h->d_cert && (e = hipMalloc(&h->d_cert, (size_t)CMPC_CERT_WORDS * h->max_batch * sizeof(double))) != hipSuccess) {
-    h->d_cert = nullptr;
-    return fail("hipMalloc(cert)", e);
-  }
+  const size_t B = (size_t)h->max_batch;
+  if (!h->d_xpred && (e = h->d_xpred.alloc(Stage::kForcesMax * B)) != hipSuccess) return fail("hipMalloc(x_pred)", e);
+  if (!h->d_cert && (e = h->d_cert.alloc(CMPC_CERT_WORDS * B)) != hipSuccess) return fail("hipMalloc(cert)", e);
   const int N = h->prm.horizon;
   const size_t rw = (size_t)CMPC_REC_WORDS(N);
-  if ((e = hipMemcpyAsync(h->d_rec, records, rw * batch * sizeof(float), hipMemcpyHostToDevice, h->stream)) != hipSuccess)
-    return fail("H2D", e);
-  if ((e = hipMemcpyAsync(h->d_forces, forces, sizeof(float) * 12 * N * batch, hipMemcpyHostToDevice, h->stream)) != hipSuccess)
-    return fail("H2D", e);
-  if (int r = cmpc_batch_evaluate(h, h->d_rec, h->d_forces, batch, xpred ? h->d_xpred : nullptr,
-                                  cert ? h->d_cert : nullptr))
+  float* d_rec = h->d_rec.get();
+  float* d_forces = h->d_forces.get();
+  if (int r = stream_h2d(h, d_rec, records, rw * batch * sizeof(float))) return r;
+  if (int r = stream_h2d(h, d_forces, forces, sizeof(float) * 12 * N * batch)) return r;
+  if (int r = cmpc_batch_evaluate(h, d_rec, d_forces, batch, xpred ? h->d_xpred.get() : nullptr,
+                                  cert ? h->d_cert.get() : nullptr))
     return r;
-  if (xpred && (e = hipMemcpyAsync(xpred, h->d_xpred, sizeof(float) * 12 * N * batch, hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
-    return fail("D2H", e);
-  if (cert && (e = hipMemcpyAsync(cert, h->d_cert, sizeof(double) * CMPC_CERT_WORDS * batch, hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
-    return fail("D2H", e);
-  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
-  return 0;
+  if (xpred)
+    if (int r = stream_d2h(h, xpred, h->d_xpred.get(), sizeof(float) * 12 * N * batch)) return r;
+  if (cert)
+    if (int r = stream_d2h(h, cert, h->d_cert.get(), sizeof(double) * CMPC_CERT_WORDS * batch)) return r;
+  return stream_sync(h);
 }
 
 // =============================================================================================
@@ -906,7 +877,7 @@ struct SingleState {
   std::vector<float> traj;
   std::vector<unsigned char> gait;
   int max_iterations = 0, use_jcqp = 0;
-  cmpc_model model = {12.0, {0.07, 0.26, 0.242}};  // cmpc_set_model: the next solve's model
+  cmpc_model model = kDefaultModel;  // cmpc_set_model: the next solve's model
   double rho = 0, sigma = 0, solver_alpha = 0, terminate = 0;
   // solve_mpc state
   std::vector<double> q_soln;
@@ -917,22 +888,22 @@ struct SingleState {
   // periodic-disturbance estimator state (SolverMPC.cpp:390-398, 555-563, 688-798): histories,
   // count and fit on the device (cmpc_estimator.hip ring of the last 400 samples); f_est,
   // f_est_smoothed and f_est_static are the exported globals below
-  float* d_est = nullptr;
+  DevBuf<float> d_est;
 };
-SingleState g;
+// (never destroyed, like the side-stream pool: its handle and estimator state live as long as the
+// process, and nothing of the runtime's is freed while the process unloads it)
+SingleState& g = *new SingleState();
 
 // The estimator state of the single-instance ABI lives on the device (one CMPC_EST_WORDS slot,
 // cmpc_estimator.hip): the same kernel as the batched config-5 path runs the reference's per-call
 // estimator step (SolverMPC.cpp:688-798) ahead of the solve, so one implementation serves both.
 int ensure_single_est(SingleState& s) {
   if (s.d_est) return 0;
-  hipError_t e = hipMalloc(&s.d_est, CMPC_EST_WORDS * sizeof(float));
-  if (e == hipSuccess) e = hipMemset(s.d_est, 0, CMPC_EST_WORDS * sizeof(float));
-  if (e != hipSuccess) {
-    if (s.d_est) (void)hipFree(s.d_est);
-    s.d_est = nullptr;
-    return fail("hipMalloc(estimator state)", e);
-  }
+  DevBuf<float> est;
+  hipError_t e = est.alloc(CMPC_EST_WORDS);
+  if (e == hipSuccess) e = hipMemset(est.get(), 0, CMPC_EST_WORDS * sizeof(float));
+  if (e != hipSuccess) return fail("hipMalloc(estimator state)", e);
+  s.d_est = std::move(est);
   return 0;
 }
 
@@ -940,66 +911,63 @@ int ensure_single_est(SingleState& s) {
 // (staged with the estimator step), host forces out.
 int admm_device(cmpc_batch* h, int N, const cmpc_admm_settings& as, float* forces, uint8_t* st) {
   const size_t n = 12 * (size_t)N;
-  float* dH = h->d_admm_H;
+  float* d_rec = h->d_rec.get();
+  float* dH = h->d_admm_H.get();
   float* dg = dH + n * n;
-  hipError_t e;
-  int rc = cmpc_batch_condense(h, h->d_rec, 1, dH, dg);
-  if (!rc) rc = cmpc_batch_admm(h, h->d_rec, dH, dg, 1, &as, h->d_forces, h->d_status, nullptr);
-  if (!rc && (e = hipMemcpyAsync(forces, h->d_forces, n * sizeof(float), hipMemcpyDeviceToHost,
-                                 h->stream)) != hipSuccess)
-    rc = fail("D2H", e);
-  if (!rc && (e = hipMemcpyAsync(st, h->d_status, 1, hipMemcpyDeviceToHost, h->stream)) != hipSuccess)
-    rc = fail("D2H", e);
-  if (!rc && (e = hipStreamSynchronize(h->stream)) != hipSuccess) rc = fail("sync", e);
-  return rc;
+  if (int r = cmpc_batch_condense(h, d_rec, 1, dH, dg)) return r;
+  if (int r = cmpc_batch_admm(h, d_rec, dH, dg, 1, &as, h->d_forces.get(), h->d_status.get(), nullptr)) return r;
+  if (int r = stream_d2h(h, forces, h->d_forces.get(), n * sizeof(float))) return r;
+  if (int r = stream_d2h(h, st, h->d_status.get(), 1)) return r;
+  return stream_sync(h);
 }
 
 // One solve_mpc call (SolverMPC.cpp:566-1089) of the single-instance ABI on the batch-1 handle:
 // one H2D of the record with (f_ext[3], simulation_time) behind it, the estimator step on the
 // device (writes f_est(3) and the use-f_est flag into the device record), then exactly one
-// solver kernel of the record's size class (launch_single) or, for use_jcqp, condense + ADMM; one
-// D2H of forces, status word and f_est(3).
+// solver kernel of the record's size class (single_round_trip) or, for use_jcqp, condense + ADMM;
+// one D2H of forces, status word and f_est(3).
 int solve_single_device(SingleState& s, const float* rec, int N, float* forces, uint8_t* st) {
   cmpc_batch* h = s.h;
   if (int r = ensure_staging(h)) return r;
   if (int r = ensure_single_est(s)) return r;
-  const size_t rw = (size_t)CMPC_REC_WORDS(N);
-  float* pin_rec = h->h_pin;
-  float* pin_out = h->h_pin + CMPC_REC_WORDS(CMPC_MAX_HORIZON) + 4;
-  std::memcpy(pin_rec, rec, rw * sizeof(float));
-  pin_rec[rw] = f_ext[3];            // diff_history.push_back(f_ext(3))  (SolverMPC.cpp:692)
-  pin_rec[rw + 1] = simulation_time; // time_history.push_back(simulation_time)  (:698)
-  float* d_out = h->d_single_out;    // [forces 12N][status word][f_est(3)]
-  uint8_t* d_st = reinterpret_cast<uint8_t*>(d_out + 12 * N);
-  hipError_t e;
-  if ((e = hipMemcpyAsync(h->d_rec, pin_rec, (rw + 2) * sizeof(float), hipMemcpyHostToDevice, h->stream)) !=
-      hipSuccess)
-    return fail("H2D", e);
-  if ((e = cmpc::launch_estimate(s.d_est, nullptr, h->d_rec + rw, h->d_rec + rw + 1, 0.f, h->d_rec, (int)rw,
-                                 nullptr, h->d_gauss, 1, h->stream, h->kp.mdl, d_out + 12 * N + 1)) != hipSuccess)
-    return fail("launch_estimate", e);
+  // diff_history.push_back(f_ext(3)), time_history.push_back(simulation_time)  (SolverMPC.cpp:692, 698)
+  const float extra[2] = {f_ext[3], simulation_time};
+  const size_t fest = Stage::status_word(N) + 1;  // f_est(3), behind the status word
   if (s.use_jcqp == 1 || s.use_jcqp == 2) {
     // use_jcqp == 1 (SolverMPC.cpp:818-838, 1057-1062): ADMM over the full QP; use_jcqp == 2
     // (:984-1053): over the reduced one; any horizon (QPs beyond 120 variables keep M^-1 in a
     // global slab)
     cmpc_admm_settings as{s.max_iterations, s.rho, s.sigma, s.solver_alpha, s.terminate,
                           s.use_jcqp == 2 ? 1 : 0};
+    if (int r = single_upload(h, rec, extra, 2, s.d_est.get())) return r;
     if (int r = admm_device(h, N, as, forces, st)) return r;
-    if ((e = hipMemcpy(&f_est[3], d_out + 12 * N + 1, sizeof(float), hipMemcpyDeviceToHost)) != hipSuccess)
-      return fail("D2H", e);
+    const hipError_t e = hipMemcpy(&f_est[3], h->d_single_out.get() + fest, sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail("D2H", e);
     return 0;
   }
-  const int n = host_reduced_size(rec, N, h->prm.f_max);
-  if ((e = cmpc::launch_single(h->d_rec, n, h->kp, d_out, d_st, h->d_iters, h->d_one, h->stream)) != hipSuccess)
-    return fail("launch_single", e);
-  if ((e = hipMemcpyAsync(pin_out, d_out, (12 * N + 2) * sizeof(float), hipMemcpyDeviceToHost, h->stream)) !=
-      hipSuccess)
-    return fail("D2H", e);
-  if ((e = hipStreamSynchronize(h->stream)) != hipSuccess) return fail("sync", e);
-  if (int r = single_handoff(h, n, pin_out, N)) return r;  // (f_est(3) at pin_out[12 N + 1] stays)
-  std::memcpy(forces, pin_out, 12 * N * sizeof(float));
-  std::memcpy(st, pin_out + 12 * N, 1);
-  std::memcpy(&f_est[3], pin_out + 12 * N + 1, sizeof(float));
+  const float* out = nullptr;
+  if (int r = single_round_trip(h, rec, extra, 2, 1, s.d_est.get(), nullptr, &out)) return r;
+  std::memcpy(forces, out, 12 * N * sizeof(float));
+  std::memcpy(st, out + Stage::status_word(N), 1);
+  std::memcpy(&f_est[3], out + fest, sizeof(float));
+  return 0;
+}
+
+// the batch-1 handle of horizon N, with the model and the parameters of this call
+int single_handle(SingleState& s, int N) {
+  if (!s.h || s.h_horizon != N) {
+    if (s.h) cmpc_batch_destroy(s.h);
+    s.h = nullptr;
+    if (int r = cmpc_batch_create(&s.h, &s.cfg, 1, nullptr)) return r;
+    s.h_horizon = N;
+  }
+  if (std::memcmp(&s.model, &s.h->model, sizeof(s.model)) != 0)
+    if (int r = cmpc_batch_set_model(s.h, &s.model)) return r;
+  cmpc_params prm = s.cfg;
+  for (int i = 0; i < 12; i++) prm.weights[i] = s.weights[i];
+  prm.alpha = s.alpha;
+  prm.max_iter = 100;  // nWSR = 100 (SolverMPC.cpp:854)
+  if (std::memcmp(&prm, &s.h->prm, sizeof(prm)) != 0) return cmpc_batch_set_params(s.h, &prm);
   return 0;
 }
 
@@ -1008,27 +976,6 @@ void solve_single(SingleState& s) {
   s.eval_ok = false;
   if (N < 1 || N > CMPC_MAX_HORIZON) {
     std::fprintf(stderr, "[cmpc] horizon %d out of range\n", N);
-    return;
-  }
-  if (!s.h || s.h_horizon != N) {
-    if (s.h) cmpc_batch_destroy(s.h);
-    s.h = nullptr;
-    if (cmpc_batch_create(&s.h, &s.cfg, 1, nullptr) != 0) {
-      std::fprintf(stderr, "[cmpc] %s\n", cmpc_last_error());
-      return;
-    }
-    s.h_horizon = N;
-  }
-  if (std::memcmp(&s.model, &s.h->model, sizeof(s.model)) != 0 && cmpc_batch_set_model(s.h, &s.model) != 0) {
-    std::fprintf(stderr, "[cmpc] %s\n", cmpc_last_error());
-    return;
-  }
-  cmpc_params prm = s.cfg;
-  for (int i = 0; i < 12; i++) prm.weights[i] = s.weights[i];
-  prm.alpha = s.alpha;
-  prm.max_iter = 100;  // nWSR = 100 (SolverMPC.cpp:854)
-  if (std::memcmp(&prm, &s.h->prm, sizeof(prm)) != 0 && cmpc_batch_set_params(s.h, &prm) != 0) {
-    std::fprintf(stderr, "[cmpc] %s\n", cmpc_last_error());
     return;
   }
 
@@ -1048,7 +995,7 @@ void solve_single(SingleState& s) {
 
   std::vector<float> forces(12 * N);
   uint8_t st = 0;
-  if (solve_single_device(s, rec.data(), N, forces.data(), &st) != 0) {
+  if (single_handle(s, N) != 0 || solve_single_device(s, rec.data(), N, forces.data(), &st) != 0) {
     std::fprintf(stderr, "[cmpc] %s\n", cmpc_last_error());
     return;
   }
@@ -1182,7 +1129,7 @@ extern "C" int cmpc_evaluate_last(float* x_pred, double* cert) {
   }
   std::vector<float> rec(CMPC_REC_WORDS(N)), forces(12 * N);
   hipError_t e = hipStreamSynchronize(g.h->stream);
-  if (e == hipSuccess) e = hipMemcpy(rec.data(), g.h->d_rec, rec.size() * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(rec.data(), g.h->d_rec.get(), rec.size() * sizeof(float), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail("D2H", e);
   for (int i = 0; i < 12 * N; i++) forces[i] = (float)g.q_soln[i];
   return cmpc_batch_evaluate_host(g.h, rec.data(), forces.data(), 1, x_pred, cert);

@@ -19,7 +19,7 @@ import os
 
 import numpy as np
 
-from .records import CmpcModel, CmpcParams, LocoParams, make_model, make_params, record_words
+from .records import CmpcModel, CmpcParams, LocoParams, make_params, record_words
 from .records import INST_WORDS, make_instance_params  # noqa: F401
 from .records import COST_WORDS, make_instance_costs  # noqa: F401
 from .records import (CERT_COST, CERT_COST0, CERT_GAP, CERT_VIOL, CERT_SWING, CERT_GRADMAX,  # noqa: F401
@@ -28,26 +28,8 @@ from .records import (CERT_COST, CERT_COST0, CERT_GAP, CERT_VIOL, CERT_SWING, CE
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CMPC_LIB", os.path.join(PKG, "libcmpc_hip.so"))
 
-# every symbol include/cmpc_solver.h declares (C linkage unless noted)
-EXPORTED_SYMBOLS = (
-    "setup_problem", "update_problem_data", "get_solution", "update_solver_settings",
-    "update_problem_data_floats", "_Z13update_x_dragf", "f_ext", "simulation_time",
-    "f_est", "f_est_smoothed", "f_est_static",
-    "cmpc_record_words", "cmpc_batch_create", "cmpc_batch_set_params", "cmpc_batch_destroy",
-    "cmpc_batch_solve", "cmpc_batch_solve_host", "cmpc_batch_set_output_steps", "cmpc_batch_set_refine",
-    "cmpc_batch_condense", "cmpc_batch_condense_rows",
-    "cmpc_batch_stream",
-    "cmpc_last_error", "cmpc_batch_enable_timing", "cmpc_batch_enable_timing_every", "cmpc_batch_read_timing", "cmpc_batch_estimate",
-    "cmpc_batch_assemble", "cmpc_batch_rollout", "cmpc_batch_admm", "cmpc_batch_expand",
-    "cmpc_batch_evaluate", "cmpc_batch_evaluate_host", "cmpc_evaluate_last",
-    "cmpc_batch_solve_due", "cmpc_batch_estimate_due",
-    "cmpc_batch_set_model", "cmpc_batch_get_model", "cmpc_set_model",
-    "cmpc_batch_set_instance_params", "cmpc_batch_instance_count",
-    "cmpc_batch_set_instance_costs", "cmpc_batch_instance_cost_count",
-    "cmpc_batch_quadprog",   # include/cmpc_quadprog.h
-)
-
 _lib = None
+_int, _flt, _dbl, _vp = ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_void_p
 _fp = ctypes.POINTER(ctypes.c_float)
 _dp = ctypes.POINTER(ctypes.c_double)
 _ip = ctypes.POINTER(ctypes.c_int)
@@ -65,6 +47,57 @@ class AdmmSettings(ctypes.Structure):
                 ("reduced", ctypes.c_int)]
 
 
+_ptr_to = ctypes.POINTER
+# Every function include/cmpc_solver.h declares (C linkage unless noted), and cmpc_quadprog.h's one:
+# name -> (restype, argtypes). load_library applies the table, and a library that lacks one of the
+# names fails there, with the name.
+_PROTOTYPES = {
+    "setup_problem": (None, [_dbl, _int, _dbl, _dbl]),
+    "update_problem_data": (None, [_dp, _dp, _dp, _dp, _dp, _dbl, _dp, _dp, _dbl, _ip]),
+    "get_solution": (_dbl, [_int]),
+    "update_solver_settings": (None, [_int, _dbl, _dbl, _dbl, _dbl, _dbl]),
+    "update_problem_data_floats": (None, [_fp, _fp, _fp, _fp, _fp, _flt, _flt, _flt, _fp, _fp, _flt, _ip]),
+    "_Z13update_x_dragf": (None, [_flt]),   # (C++ linkage, as the reference declares it)
+    "cmpc_record_words": (_int, [_int]),
+    "cmpc_last_error": (ctypes.c_char_p, []),
+    "cmpc_batch_create": (_int, [_ptr_to(_vp), _ptr_to(CmpcParams), _int, _vp]),
+    "cmpc_batch_set_params": (_int, [_vp, _ptr_to(CmpcParams)]),
+    "cmpc_batch_destroy": (None, [_vp]),
+    "cmpc_batch_stream": (_vp, [_vp]),
+    "cmpc_batch_set_output_steps": (_int, [_vp, _int]),
+    "cmpc_batch_set_refine": (_int, [_vp, _int]),
+    "cmpc_batch_set_model": (_int, [_vp, _ptr_to(CmpcModel)]),
+    "cmpc_batch_get_model": (_int, [_vp, _ptr_to(CmpcModel)]),
+    "cmpc_set_model": (_int, [_ptr_to(CmpcModel)]),
+    "cmpc_batch_set_instance_params": (_int, [_vp, _vp, _int]),
+    "cmpc_batch_instance_count": (_int, [_vp]),
+    "cmpc_batch_set_instance_costs": (_int, [_vp, _vp, _int]),
+    "cmpc_batch_instance_cost_count": (_int, [_vp]),
+    "cmpc_batch_solve": (_int, [_vp, _vp, _int, _vp, _vp, _vp]),
+    "cmpc_batch_solve_due": (_int, [_vp, _vp, _vp, _int, _vp, _vp, _vp]),
+    "cmpc_batch_solve_host": (_int, [_vp, _fp, _int, _fp, _u8p, _ip]),
+    "cmpc_batch_estimate": (_int, [_vp, _vp, _vp, _vp, _vp, _flt, _vp, _vp, _int]),
+    "cmpc_batch_estimate_due": (_int, [_vp, _vp, _vp, _vp, _vp, _flt, _vp, _vp, _vp, _int]),
+    "cmpc_batch_condense": (_int, [_vp, _vp, _int, _vp, _vp]),
+    "cmpc_batch_condense_rows": (_int, [_vp, _vp, _int, _vp, _vp]),
+    "cmpc_batch_admm": (_int, [_vp, _vp, _vp, _vp, _int, _ptr_to(AdmmSettings), _vp, _vp, _vp]),
+    "cmpc_batch_assemble": (_int, [_vp, _vp, _ptr_to(LocoParams), _vp, _vp, _int]),
+    "cmpc_batch_expand": (_int, [_vp, _vp, _vp, _int]),
+    "cmpc_batch_rollout": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int]),
+    "cmpc_batch_evaluate": (_int, [_vp, _vp, _vp, _int, _vp, _vp]),
+    "cmpc_batch_evaluate_host": (_int, [_vp, _fp, _fp, _int, _fp, _dp]),
+    "cmpc_evaluate_last": (_int, [_fp, _dp]),
+    "cmpc_batch_enable_timing": (_int, [_vp, _int]),
+    "cmpc_batch_enable_timing_every": (_int, [_vp, _int, _int]),
+    "cmpc_batch_read_timing": (_int, [_vp, _fp, _ip, _ip]),
+    "cmpc_batch_quadprog": (_int, [_vp, _int, _int, _int] + [_vp] * 7 + [_int] + [_vp] * 4 + [_int]),
+}
+# the data symbols: the caller-owned f_ext and simulation_time, the estimator's three globals
+_DATA_SYMBOLS = ("f_ext", "simulation_time", "f_est", "f_est_smoothed", "f_est_static")
+# every symbol the headers declare (tests/test_host.py holds the library's exports against it)
+EXPORTED_SYMBOLS = tuple(_PROTOTYPES) + _DATA_SYMBOLS
+
+
 def admm_settings(max_iter: int = 10000, rho: float = 1e-7, sigma: float = 1e-8,
                   alpha: float = 1.5, terminate: float = 0.1, reduced: bool = False) -> AdmmSettings:
     return AdmmSettings(int(max_iter), float(rho), float(sigma), float(alpha), float(terminate),
@@ -80,77 +113,17 @@ def load_library(path: str = LIB_PATH):
         raise CmpcError(f"{path} not built: run __graft_entry__.build() "
                         f"(or python quad-periodic-mpc_amd/build.py)")
     lib = ctypes.CDLL(path, mode=ctypes.RTLD_GLOBAL)
-    lib.setup_problem.argtypes = [ctypes.c_double, ctypes.c_int, ctypes.c_double, ctypes.c_double]
-    lib.update_problem_data.argtypes = [_dp, _dp, _dp, _dp, _dp, ctypes.c_double, _dp, _dp,
-                                        ctypes.c_double, _ip]
-    lib.get_solution.argtypes = [ctypes.c_int]
-    lib.get_solution.restype = ctypes.c_double
-    lib.update_solver_settings.argtypes = [ctypes.c_int, ctypes.c_double, ctypes.c_double,
-                                           ctypes.c_double, ctypes.c_double, ctypes.c_double]
-    lib.update_problem_data_floats.argtypes = [_fp, _fp, _fp, _fp, _fp, ctypes.c_float,
-                                               ctypes.c_float, ctypes.c_float, _fp, _fp,
-                                               ctypes.c_float, _ip]
-    lib._Z13update_x_dragf.argtypes = [ctypes.c_float]
-    lib.cmpc_record_words.argtypes = [ctypes.c_int]
-    lib.cmpc_batch_create.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(CmpcParams),
-                                      ctypes.c_int, ctypes.c_void_p]
-    lib.cmpc_batch_set_params.argtypes = [ctypes.c_void_p, ctypes.POINTER(CmpcParams)]
-    lib.cmpc_batch_destroy.argtypes = [ctypes.c_void_p]
-    lib.cmpc_batch_destroy.restype = None
-    lib.cmpc_batch_solve.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.cmpc_batch_solve_host.argtypes = [ctypes.c_void_p, _fp, ctypes.c_int, _fp, _u8p, _ip]
-    lib.cmpc_batch_set_output_steps.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    if hasattr(lib, "cmpc_batch_set_refine"):  # (older A/B variant libraries lack it)
-        lib.cmpc_batch_set_refine.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    lib.cmpc_batch_condense.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                        ctypes.c_void_p, ctypes.c_void_p]
-    if hasattr(lib, "cmpc_batch_condense_rows"):  # (older A/B variant libraries lack it)
-        lib.cmpc_batch_condense_rows.argtypes = lib.cmpc_batch_condense.argtypes
-    lib.cmpc_batch_admm.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                    ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(AdmmSettings),
-                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    lib.cmpc_batch_stream.argtypes = [ctypes.c_void_p]
-    lib.cmpc_batch_expand.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-    lib.cmpc_batch_stream.restype = ctypes.c_void_p
-    lib.cmpc_last_error.restype = ctypes.c_char_p
-    lib.cmpc_batch_enable_timing.argtypes = [ctypes.c_void_p, ctypes.c_int]
-    if hasattr(lib, "cmpc_batch_enable_timing_every"):  # (A/B libraries built before round 4 lack it)
-        lib.cmpc_batch_enable_timing_every.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
-    lib.cmpc_batch_read_timing.argtypes = [ctypes.c_void_p, _fp, _ip, _ip]
-    lib.cmpc_batch_estimate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
-                                        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-    if hasattr(lib, "cmpc_batch_solve_due"):  # (A/B libraries built before the due forms lack them)
-        lib.cmpc_batch_solve_due.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                             ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-        lib.cmpc_batch_estimate_due.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float,
-                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                                ctypes.c_int]
-    lib.cmpc_batch_assemble.argtypes = [ctypes.c_void_p, ctypes.c_void_p,
-                                        ctypes.POINTER(LocoParams), ctypes.c_void_p,
-                                        ctypes.c_void_p, ctypes.c_int]
-    lib.cmpc_batch_rollout.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                       ctypes.c_int]
-    if hasattr(lib, "cmpc_batch_evaluate"):  # (A/B libraries built before the evaluate unit lack it)
-        lib.cmpc_batch_evaluate.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                            ctypes.c_void_p, ctypes.c_void_p]
-        lib.cmpc_batch_evaluate_host.argtypes = [ctypes.c_void_p, _fp, _fp, ctypes.c_int, _fp, _dp]
-        lib.cmpc_evaluate_last.argtypes = [_fp, _dp]
-    if hasattr(lib, "cmpc_batch_set_model"):  # (A/B libraries built before the model was a parameter lack it)
-        lib.cmpc_batch_set_model.argtypes = [ctypes.c_void_p, ctypes.POINTER(CmpcModel)]
-        lib.cmpc_batch_get_model.argtypes = [ctypes.c_void_p, ctypes.POINTER(CmpcModel)]
-        lib.cmpc_set_model.argtypes = [ctypes.POINTER(CmpcModel)]
-    if hasattr(lib, "cmpc_batch_set_instance_params"):  # (A/B libraries built before the table lack it)
-        lib.cmpc_batch_set_instance_params.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        lib.cmpc_batch_instance_count.argtypes = [ctypes.c_void_p]
-    if hasattr(lib, "cmpc_batch_set_instance_costs"):  # (likewise)
-        lib.cmpc_batch_set_instance_costs.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        lib.cmpc_batch_instance_cost_count.argtypes = [ctypes.c_void_p]
-    lib.cmpc_batch_quadprog.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int] + \
-        [ctypes.c_void_p] * 7 + [ctypes.c_int] + [ctypes.c_void_p] * 4 + [ctypes.c_int]
+    for name, (restype, argtypes) in _PROTOTYPES.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            raise CmpcError(f"{path} does not export {name}") from None
+        fn.restype, fn.argtypes = restype, argtypes
+    for name in _DATA_SYMBOLS:
+        try:
+            ctypes.c_float.in_dll(lib, name)
+        except ValueError:
+            raise CmpcError(f"{path} does not export {name}") from None
     _lib = lib
     return lib
 
@@ -169,6 +142,9 @@ def _f32(a, n=None):
     if n is not None and a.size < n:
         raise ValueError(f"expected >= {n} floats, got {a.size}")
     return a
+
+
+_setup_horizon = 0  # horizon of the last setup_problem (the steps evaluate_last returns)
 
 
 def setup_problem(dt: float, horizon: int, mu: float, f_max: float) -> None:
@@ -209,10 +185,7 @@ def update_problem_data(p, v, q, w, r, yaw, weights, state_trajectory, alpha, ga
 def set_model(model: CmpcModel | None) -> None:
     """``cmpc_set_model``: the robot model of the single-instance surface from the next
     ``update_problem_data*`` call on (``None``: the default, m = 12, I = diag(.07, .26, .242))."""
-    lib = load_library()
-    if not hasattr(lib, "cmpc_set_model"):
-        raise CmpcError("this libcmpc_hip.so has no cmpc_set_model")
-    _check(lib.cmpc_set_model(ctypes.byref(model) if model is not None else None), "cmpc_set_model")
+    _check(load_library().cmpc_set_model(ctypes.byref(model) if model is not None else None), "cmpc_set_model")
 
 
 def get_solution(index: int) -> float:
@@ -229,9 +202,6 @@ def evaluate_last():
     _check(lib.cmpc_evaluate_last(x_pred.ctypes.data_as(_fp), cert.ctypes.data_as(_dp)),
            "cmpc_evaluate_last")
     return x_pred[:12 * _setup_horizon].reshape(-1, 12).copy(), cert
-
-
-_setup_horizon = 0  # horizon of the last setup_problem (the steps evaluate_last returns)
 
 
 def set_f_ext(values) -> None:
@@ -274,6 +244,8 @@ class BatchSolver:
         self.lib = load_library()
         self.params = params if params is not None else make_params(horizon)
         self.max_batch = int(max_batch)
+        self._out_steps = 0      # set_output_steps (0: every step)
+        self._timing_steps = 0   # enable_timing
         h = ctypes.c_void_p()
         s = None
         if stream is not None:
@@ -301,19 +273,35 @@ class BatchSolver:
         """The handle's robot model (``cmpc_batch_set_model``; ``None``: the default). Handle state
         of its own: it survives :meth:`set_params` and applies to every call made after it. A
         non-finite or non-positive field raises and leaves the handle's model as it was."""
-        if not hasattr(self.lib, "cmpc_batch_set_model"):
-            raise CmpcError("this libcmpc_hip.so has no cmpc_batch_set_model")
         _check(self.lib.cmpc_batch_set_model(self._h, ctypes.byref(model) if model is not None else None),
                "cmpc_batch_set_model")
 
     @property
     def model(self) -> CmpcModel:
         """The handle's robot model as the library holds it (``cmpc_batch_get_model``)."""
-        if not hasattr(self.lib, "cmpc_batch_get_model"):
-            return make_model()
         m = CmpcModel()
         _check(self.lib.cmpc_batch_get_model(self._h, ctypes.byref(m)), "cmpc_batch_get_model")
         return m
+
+    def _set_table(self, table, dtype, words: int, fn_name: str) -> None:
+        """Upload of a per-instance table through ``fn_name``: ``table`` is ``[B, words]`` of
+        ``dtype``, a numpy array (uploaded here) or a CUDA tensor; ``None`` clears it."""
+        fn = getattr(self.lib, fn_name)
+        who = fn_name[len("cmpc_batch_"):]
+        if table is None:
+            _check(fn(self._h, None, 0), fn_name)
+            return
+        import torch
+        if hasattr(table, "data_ptr"):
+            if table.dtype != getattr(torch, dtype) or not table.is_cuda:
+                raise CmpcError(f"{who}: a tensor table must be {dtype} on the device")
+            dev = table
+        else:
+            dev = torch.from_numpy(np.ascontiguousarray(table, getattr(np, dtype))).cuda()
+        if dev.dim() != 2 or dev.shape[1] != words or not dev.is_contiguous():
+            raise CmpcError(f"{who}: the table must be contiguous [B, {words}], got {tuple(dev.shape)}")
+        torch.cuda.current_stream().synchronize()  # the upload, or the caller's writes, before the snapshot
+        _check(fn(self._h, dev.data_ptr(), int(dev.shape[0])), fn_name)
 
     def set_instance_params(self, table) -> None:
         """Per-instance mass, inertia, friction coefficient and force limit
@@ -322,30 +310,11 @@ class BatchSolver:
         array (uploaded here) or a float64 CUDA tensor; row i belongs to instance i of every later
         call. The library snapshots the rows; ``None`` clears the table (the handle's shared model,
         mu and f_max again). A bad row raises (-2) and leaves the previous table, or none, in force."""
-        if not hasattr(self.lib, "cmpc_batch_set_instance_params"):
-            raise CmpcError("this libcmpc_hip.so has no cmpc_batch_set_instance_params")
-        if table is None:
-            _check(self.lib.cmpc_batch_set_instance_params(self._h, None, 0), "cmpc_batch_set_instance_params")
-            return
-        import torch
-        if hasattr(table, "data_ptr"):
-            if table.dtype != torch.float64 or not table.is_cuda:
-                raise CmpcError("set_instance_params: a tensor table must be float64 on the device")
-            dev = table
-        else:
-            dev = torch.from_numpy(np.ascontiguousarray(table, np.float64)).cuda()
-        if dev.dim() != 2 or dev.shape[1] != INST_WORDS or not dev.is_contiguous():
-            raise CmpcError(f"set_instance_params: the table must be contiguous [B, {INST_WORDS}], "
-                            f"got {tuple(dev.shape)}")
-        torch.cuda.current_stream().synchronize()  # the upload, or the caller's writes, before the snapshot
-        _check(self.lib.cmpc_batch_set_instance_params(self._h, dev.data_ptr(), int(dev.shape[0])),
-               "cmpc_batch_set_instance_params")
+        self._set_table(table, "float64", INST_WORDS, "cmpc_batch_set_instance_params")
 
     @property
     def instance_count(self) -> int:
         """Rows of the per-instance table in force (``cmpc_batch_instance_count``; 0: none set)."""
-        if not hasattr(self.lib, "cmpc_batch_instance_count"):
-            return 0
         return int(self.lib.cmpc_batch_instance_count(self._h))
 
     def set_instance_costs(self, table) -> None:
@@ -355,29 +324,10 @@ class BatchSolver:
         later call. The library snapshots the rows; ``None`` clears the table (the handle's shared
         weights and alpha again). Independent of :meth:`set_instance_params`. A bad row raises (-2)
         and leaves the previous table, or none, in force."""
-        if not hasattr(self.lib, "cmpc_batch_set_instance_costs"):
-            raise CmpcError("this libcmpc_hip.so has no cmpc_batch_set_instance_costs")
-        if table is None:
-            _check(self.lib.cmpc_batch_set_instance_costs(self._h, None, 0), "cmpc_batch_set_instance_costs")
-            return
-        import torch
-        if hasattr(table, "data_ptr"):
-            if table.dtype != torch.float32 or not table.is_cuda:
-                raise CmpcError("set_instance_costs: a tensor table must be float32 on the device")
-            dev = table
-        else:
-            dev = torch.from_numpy(np.ascontiguousarray(table, np.float32)).cuda()
-        if dev.dim() != 2 or dev.shape[1] != COST_WORDS or not dev.is_contiguous():
-            raise CmpcError(f"set_instance_costs: the table must be contiguous [B, {COST_WORDS}], "
-                            f"got {tuple(dev.shape)}")
-        torch.cuda.current_stream().synchronize()  # the upload, or the caller's writes, before the snapshot
-        _check(self.lib.cmpc_batch_set_instance_costs(self._h, dev.data_ptr(), int(dev.shape[0])),
-               "cmpc_batch_set_instance_costs")
+        self._set_table(table, "float32", COST_WORDS, "cmpc_batch_set_instance_costs")
 
     def instance_cost_count(self) -> int:
         """Rows of the cost table in force (``cmpc_batch_instance_cost_count``; 0: none set)."""
-        if not hasattr(self.lib, "cmpc_batch_instance_cost_count"):
-            return 0
         return int(self.lib.cmpc_batch_instance_cost_count(self._h))
 
     @property
@@ -387,8 +337,7 @@ class BatchSolver:
     @property
     def out_cols(self) -> int:
         """Forces kept per instance (12 x the output steps, 12 N by default)."""
-        steps = getattr(self, "_out_steps", 0)
-        return 12 * (steps if 0 < steps < self.horizon else self.horizon)
+        return 12 * (self._out_steps if 0 < self._out_steps < self.horizon else self.horizon)
 
     def set_output_steps(self, steps: int) -> None:
         """Keep the forces of the first ``steps`` horizon steps only (0: every step);
@@ -611,17 +560,11 @@ class BatchSolver:
         """Record HIP events around each size-class launch of the next ``steps`` solves (of every
         ``every``-th solve only, ``steps`` of them, when ``every`` > 1)."""
         self._timing_steps = int(steps)
-        if not hasattr(self.lib, "cmpc_batch_enable_timing_every"):
-            if every != 1:
-                raise CmpcError("this libcmpc_hip.so has no cmpc_batch_enable_timing_every")
-            _check(self.lib.cmpc_batch_enable_timing(self._h, int(steps)), "enable_timing")
-            return
         _check(self.lib.cmpc_batch_enable_timing_every(self._h, int(steps), int(every)), "enable_timing")
 
     def read_timing(self):
         """-> (ms [steps, 2] per class launch, class-1 overflow count of the last solve)."""
-        n = getattr(self, "_timing_steps", 0)
-        ms = np.zeros(2 * max(n, 1), np.float32)
+        ms = np.zeros(2 * max(self._timing_steps, 1), np.float32)
         rec = ctypes.c_int(0)
         ovf = ctypes.c_int(0)
         _check(self.lib.cmpc_batch_read_timing(self._h, ms.ctypes.data_as(_fp), ctypes.byref(rec),

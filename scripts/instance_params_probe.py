@@ -15,7 +15,8 @@ for bit between the forms.
 
   python scripts/instance_params_probe.py [--batch 65536] [--reps 50] [--forms shared,table,shared_again]
 
-(--forms: a library from before the cost table, named by CMPC_LIB, runs the first two forms only)
+(--forms picks the forms and their order; a library named by CMPC_LIB must export every symbol the
+binding declares, as every library this tree builds does)
 """
 import argparse
 import importlib
