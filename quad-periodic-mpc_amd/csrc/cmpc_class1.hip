@@ -17,7 +17,7 @@
 //     publishes it, and the broadcast reads are ds_read_b128; the Cholesky's trailing sweep and
 //     the active set's reflection take the broadcast from lane c's register instead, as 4x4x1
 //     MFMA outer products with the A-operand broadcast;
-//   * J = L^-T is solved left-looking inside the factorisation's pair steps: the stored columns
+//   * J = L^-T is solved left-looking inside the factorisation's panels: the stored columns
 //     are -L's, lane v keeps x_j = J[v][j] in the registers of the finished H columns, and each
 //     step adds the row sums over the finished columns (16-B broadcasts, four rows per read);
 //   * the QP's triangular factor R is explicit, packed upper columns in the LDS region that held
@@ -198,6 +198,41 @@ __device__ __forceinline__ void pin_range(float (&x)[M]) {
   for (int c = C0; c < C1; c++) asm volatile("" : "+v"(x[c]));
 }
 
+// piped_sweep (cmpc_common.h) with other work under its first loads: under() runs once the first
+// group's loads are issued and before any of the sweep's arithmetic, so the wave meets the LDS
+// latency beneath that work. under() must not store to what ld reads.
+template <int C0, int CE, int GRP, class U, class Ld, class F>
+__device__ __forceinline__ void piped_sweep_under(U&& under, Ld&& ld, F&& f) {
+  constexpr int NCH = (CE > C0) ? (CE - C0) / 4 : 0;
+  if constexpr (NCH == 0) {
+    under();
+  } else {
+    using T = decltype(ld(std::integral_constant<int, C0>{}));
+    constexpr int NG = (NCH + GRP - 1) / GRP;
+    T cur[GRP], nxt[GRP];
+    static_for<0, GRP>([&](auto I) {
+      constexpr int ch = decltype(I)::value;
+      if constexpr (ch < NCH) cur[ch] = ld(std::integral_constant<int, C0 + 4 * ch>{});
+    });
+    __builtin_amdgcn_sched_barrier(0);
+    under();
+    static_for<0, NG>([&](auto GI) {
+      constexpr int g = decltype(GI)::value;
+      static_for<0, GRP>([&](auto I) {
+        constexpr int ch = (g + 1) * GRP + decltype(I)::value;
+        if constexpr (ch < NCH) nxt[decltype(I)::value] = ld(std::integral_constant<int, C0 + 4 * ch>{});
+      });
+      __builtin_amdgcn_sched_barrier(0);
+      static_for<0, GRP>([&](auto I) {
+        constexpr int ch = g * GRP + decltype(I)::value;
+        if constexpr (ch < NCH) f(std::integral_constant<int, C0 + 4 * ch>{}, cur[decltype(I)::value]);
+      });
+      __builtin_amdgcn_sched_barrier(0);
+      static_for<0, GRP>([&](auto I) { cur[decltype(I)::value] = nxt[decltype(I)::value]; });
+    });
+  }
+}
+
 // A value at a wave-uniform address of read-only global memory re-read where it is used, as
 // karg_late does for the argument segment: a scalar load behind a pointer the optimiser cannot
 // see through, so the value holds SGPRs only around its use
@@ -207,6 +242,23 @@ __device__ __forceinline__ T cmem_late(const void* base, int off) {
   cptr p = (cptr)(uintptr_t)base;
   asm volatile("" : "+s"(p));
   return *reinterpret_cast<const __attribute__((address_space(4))) T*>(p + off);
+}
+
+// step_proj (cmpc_common.h) with its derived constants passed in: dt2 = 2 dt, dtq = 2 (dt^2 / 2),
+// dtc = dt^3 / 3 and imx = (1 / m) x_drag, each formed as step_proj forms it
+__device__ __forceinline__ void step_proj_c(const Model& md, const CondGeo& cg, const float* z, float dt2,
+                                            float dtq, float dtc, float imx, StepProj& pj) {
+  const float im = md.im;
+  float q[3];
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+    q[i] = fmaf(dt2, z[6 + i], dtq * fmaf(md.R[i * 3 + 2], z[2], fmaf(md.R[i * 3 + 1], z[1], md.R[i * 3] * z[0])));
+#pragma unroll
+  for (int j = 0; j < 3; j++)
+    pj.w[j] = fmaf(cg.Ii[6 + j], q[2], fmaf(cg.Ii[3 + j], q[1], cg.Ii[j] * q[0]));
+#pragma unroll
+  for (int a = 0; a < 3; a++) pj.p[a] = im * fmaf(dt2, z[9 + a], dtq * z[3 + a]);
+  pj.p[0] = fmaf(imx, fmaf(dtq, z[11], dtc * z[5]), pj.p[0]);
 }
 
 // Element q (LO <= q < HI, wave-uniform: an SGPR) of a register-resident row, as a tree of scalar
@@ -370,6 +422,10 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       ms.dt = rfl(md.dt); ms.dth = rfl(md.dth); ms.xdrag = rfl(md.xdrag); ms.im = rfl(md.im);
 #pragma unroll
       for (int j = 0; j < 3; j++) ms.ib[j] = md.ib[j];
+      // step_proj's derived constants, formed once ahead of the steps (no step's condition
+      // dominates the next one's, so each step formed them again) and kept in SGPRs
+      const float dt2 = rfl(2.f * ms.dt), dtq = rfl(2.f * ms.dth), dtc = rfl(ms.dt * ms.dt * ms.dt / 3.f);
+      const float imx = rfl(ms.im * ms.xdrag);
       static_for<0, NV / 6>([&](auto IC) {
         constexpr int i = NV / 6 - 1 - decltype(IC)::value;
         if (i < N) {
@@ -401,27 +457,20 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
           }
           const float alpha2 = cost_alpha2<INST>(P, ie);
           StepProj pj;
-          step_proj(ms, cg, z, pj);
+          step_proj_c(ms, cg, z, dt2, dtq, dtc, imx, pj);
           // (the ballot opaque: the step's nibble is shifted out here, not kept from the test above)
           unsigned long long mo0 = msk0;
           asm volatile("" : "+s"(mo0));
           const unsigned mi = step_mask(mo0, 0ull, i);  // (i < 16: the first ballot alone)
-          // the foot positions likewise, from the record in global memory (the values of cg.r)
-          const kf32x4 p0 = cmem_late<kf32x4>(rec, 4 * CMPC_REC_R), p1 = cmem_late<kf32x4>(rec, 4 * CMPC_REC_R + 16),
-                       p2 = cmem_late<kf32x4>(rec, 4 * CMPC_REC_R + 32);
-          const float rs[12] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w, p2.x, p2.y, p2.z, p2.w};
           static_for<0, 2>([&](auto SC) {
             constexpr int s = decltype(SC)::value;
-            // the step's s-th stance foot: lowest / next set bit of the nibble, its position
-            // selected among the twelve uniform values
+            // the step's s-th stance foot: lowest / next set bit of the nibble (an SGPR). Its
+            // position likewise comes from the record in global memory (the values of cg.r), three
+            // scalar loads at the foot's offset: no select among the twelve words
             const int f = __builtin_ctz(s == 0 ? mi : (mi & (mi - 1u)));
-            // (through sopq: a select between the array's elements as they stand becomes a select
-            // of their addresses, and the array goes to scratch)
-            const auto foot = [&](int j) {
-              const float a0 = sopq(rs[j]), a1 = sopq(rs[j + 1]), a2 = sopq(rs[j + 2]), a3 = sopq(rs[j + 3]);
-              return (f & 2) ? ((f & 1) ? a3 : a2) : ((f & 1) ? a1 : a0);
-            };
-            const float r0 = foot(0), r1 = foot(4), r2 = foot(8);
+            const float r0 = cmem_late<float>(rec, 4 * (CMPC_REC_R + f)),
+                        r1 = cmem_late<float>(rec, 4 * (CMPC_REC_R + 4 + f)),
+                        r2 = cmem_late<float>(rec, 4 * (CMPC_REC_R + 8 + f));
             float val[3];
             foot_entries(pj, r0, r1, r2, val);
             static_for<0, 3>([&](auto AC) {
@@ -487,20 +536,31 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
   }
 
   // ---- bordered Cholesky [H | g] with J = L^-T and x = -J y solved inside it ----------------
-  // Column k of the working matrix is slot[k] of every lane. Two pivots per step (k even, k+1):
-  // one rank-2 sweep over the raw column k and column k+1 as it is after step k,
-  //   slot[c] += a0 P_k[c] + a1 P_k+1[c]  (c >= k+2),  a0 = -H[v][k] / d_k,  a1 = -s1 / d_k+1,
-  //   s1 = H[v][k+1] - beta H[v][k],  beta = H[k+1][k] / d_k,  d_k+1 = H[k+1][k+1] - beta H[k+1][k]
-  // so NV / 2 serial steps (pivot, broadcast) do the work of NV. The sweep takes both columns
-  // from the registers of the lanes that own them, as MFMA outer products (mfma_chunk); the
-  // columns are also stored to P (one ds_write_b32 each), where only the J sums read them.
-  // Look-ahead: as soon as the sweep chunk holding columns k+2, k+3 is updated, the step takes
-  // their pivot data by readlane, forms the next step's beta / d / 1/sqrt(d), and publishes
-  // column k+2 and the corrected column k+3; so the next step starts on its sweep at once. The
-  // stored columns (raw even, corrected odd) are what J = L^-T needs. Odd n: the last step's
-  // second pivot is the identity padding row (H[n][n] = 1, no coupling).
-  // Each pair step then finishes rows k, k+1 of J left-looking from the stored columns, and adds
-  // their terms to x = -J y, so the stage ends with J in slot[0..NV) and the unconstrained
+  // Column k of the working matrix is slot[k] of every lane. Pivots come in pairs (j even, j+1):
+  // a pair's rank-2 update takes the raw column j and column j+1 as it is after pivot j,
+  //   slot[c] += a0 P_j[c] + a1 P_j+1[c]  (c >= j+2),  a0 = -H[v][j] / d_j,  a1 = -s1 / d_j+1,
+  //   s1 = H[v][j+1] - beta H[v][j],  beta = H[j+1][j] / d_j,  d_j+1 = H[j+1][j+1] - beta H[j+1][j]
+  // and look(j) forms a pair's beta / d / 1/sqrt(d) by readlane and publishes column j and the
+  // corrected column j+1: one element per lane in a register (pub), and stored to P (one
+  // ds_write_b32 each), where only the J sums of later panels read them. The stored columns (raw
+  // even, corrected odd) are what J = L^-T needs.
+  // A step is a panel of four pivots k .. k+3 (k = 0 mod 4: a sweep chunk), so NV / 4 serial steps:
+  //   * pair (k, k+1) from the look before; its update of columns k+2, k+3 is two FMAs per column
+  //     in the VALU, on the values lanes k+2, k+3 hold of the two published columns (what the MFMA
+  //     would broadcast, and one fmaf like it), pivot k's before pivot k+1's;
+  //   * look(k+2) on the now-final columns k+2, k+3, and the second pair's coefficients;
+  //   * one rank-4 sweep over the chunks c >= k+4, the columns taken from the registers of the
+  //     lanes that own them as MFMA outer products (mfma_chunk). The chunk at k+4 takes all four
+  //     pivots first and look(k+4), the next panel's, follows it at once; the other chunks take all
+  //     of pivot k, then all of k+1, k+2, k+3 (MFMAs on one accumulator a sweep apart). Every
+  //     element gets its four FMAs in pivot order, as NV / 2 rank-2 steps would give them;
+  //   * rows k .. k+3 of J, left-looking: their sums over the finished columns q < k read only what
+  //     earlier panels stored, the triangular solve inside the panel takes its five multipliers
+  //     by readlane from the published registers; their terms are added to x = -J y.
+  // The second pair of a panel (the update of columns k+2, k+3, look(k+2), pivots k+2, k+3 of the
+  // sweep, rows k+2, k+3 of J) runs only if k+2 < n (wave-uniform); rows and columns past n stay
+  // the identity padding. Odd n: the last pair's second pivot is the identity padding row
+  // (H[n][n] = 1, no coupling). The stage ends with J in slot[0..NV) and the unconstrained
   // minimiser in xunc.
   int status = CMPC_OK;
   float i0n = 1.f, betan = 0.f, i1n = 1.f, g0n = 0.f, g1n = 0.f;
@@ -528,7 +588,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
     g0n = -g0n * i0n;
     g1n = -g1n * i1n;
     // the sweep takes the columns from these registers; the stores feed only the J sums, which
-    // order themselves after them (lsync ahead of the sums)
+    // belong to later panels and order themselves after them (lsync at the top of a panel)
     pub0n = (v >= j) ? -slot[j] * i0n : 0.f;
     pub1n = (v >= j1) ? -s1 * i1n : 0.f;
     if (v >= cj && v < NV) sh.P[G::prow(j) + v - cj] = pub0n;
@@ -536,54 +596,91 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
     }
   };
   if (n > 0) look(std::integral_constant<int, 0>{});
-  float jc2 = 0.f, jc3 = 0.f;  // rows k+2, k+3 of J's sums, carried one pair step
-  // x = -J y accumulated as J's entries are solved: y_k = -g0 of pair step k (the border of row k
-  // after the pivots before it, scaled by -1/sqrt(d_k) in look)
+  // x = -J y accumulated as J's entries are solved: y_j = -g of pivot j (the border of row j
+  // after the pivots before it, scaled by -1/sqrt(d_j) in look)
   float xunc = 0.f;
-  static_for<0, NV / 2>([&](auto KB) {
-    constexpr int k = 2 * decltype(KB)::value;
-    constexpr int k1 = k + 1, k2 = k + 2;
-    constexpr int c2 = k2 & ~3;
+  static_for<0, NV / 4>([&](auto KB) {
+    constexpr int k = 4 * decltype(KB)::value;
+    constexpr int k1 = k + 1, k2 = k + 2, k3 = k + 3, c4 = k + 4;
     if (k < n) {
-      const float i0 = i0n, beta = betan, i1 = i1n, g0 = g0n, g1 = g1n;
+      // (the J sums read columns stored by earlier panels: ordered after those stores here, and
+      // free to move above this panel's own)
+      lsync();
+      const bool half2 = k2 < n;  // the second pair runs (wave-uniform)
+      // the pair's uniform values in SGPRs: they stay live down to the panel's J rows
+      const float i0 = rfl(i0n), i1 = rfl(i1n), g0 = rfl(g0n), g1 = rfl(g1n);
+      const float p0 = pub0n, p1 = pub1n;
       const float s0 = slot[k];
-      const float s1 = fmaf(-s0, beta, slot[k1]);
+      const float s1 = fmaf(-s0, betan, slot[k1]);
       // row v of L in columns k, k+1 (the sweep adds l_vk P'_k + l_vk+1 P'_k+1, P' = -L)
       const float a0 = (v > k) ? s0 * i0 : 0.f;
       const float a1 = (v > k1) ? s1 * i1 : 0.f;
       slot[NV] = fmaf(a1, g1, fmaf(a0, g0, slot[NV]));
-      // slot[c] += a0 P'_k[c] + a1 P'_k+1[c] with P'[c] taken from lane c's register. The chunk
-      // with columns k+2, k+3 takes both pivots first (the look-ahead follows it); the others
-      // all of pivot k, then all of pivot k+1, so that two MFMAs on one accumulator sit a
-      // sweep apart. Each element still gets pivot k's FMA before pivot k+1's, as above.
-      if constexpr (c2 < NV) {
-        const float p0 = pub0n, p1 = pub1n;
-        mfma_chunk<c2>(p0, a0, slot[c2 + 0], slot[c2 + 1], slot[c2 + 2], slot[c2 + 3]);
-        mfma_chunk<c2>(p1, a1, slot[c2 + 0], slot[c2 + 1], slot[c2 + 2], slot[c2 + 3]);
-        if constexpr (k2 < NV) {
-          if (k2 < n) look(std::integral_constant<int, k2>{});  // columns k+2, k+3 are final
+      // the multipliers inside the panel, -L[r][c] for k <= c < r <= k+3 and c <= k+1, as lane r
+      // holds them of the published columns: the in-panel update and the J rows both take them
+      const float hk = rl(p0, k1);
+      const float l02 = rl(p0, k2), l03 = rl(p0, k3), l12 = rl(p1, k2), l13 = rl(p1, k3);
+      float i2 = 1.f, i3 = 1.f, g2 = 0.f, g3 = 0.f, hk2 = 0.f;
+      float a2 = 0.f, a3 = 0.f, p2 = 0.f, p3 = 0.f;
+      if (half2) {
+        // columns k+2, k+3 of every lane take pivots k, k+1; then they are final
+        slot[k2] = fmaf(l12, a1, fmaf(l02, a0, slot[k2]));
+        slot[k3] = fmaf(l13, a1, fmaf(l03, a0, slot[k3]));
+        look(std::integral_constant<int, k2>{});
+        i2 = rfl(i0n); i3 = rfl(i1n); g2 = rfl(g0n); g3 = rfl(g1n);
+        p2 = pub0n; p3 = pub1n;
+        hk2 = rl(p2, k3);
+        const float s2 = slot[k2];
+        const float s3 = fmaf(-s2, betan, slot[k3]);
+        a2 = (v > k2) ? s2 * i2 : 0.f;
+        a3 = (v > k3) ? s3 * i3 : 0.f;
+        slot[NV] = fmaf(a3, g3, fmaf(a2, g2, slot[NV]));
+      }
+      // slot[c] += a0 P'_k[c] + ... + a3 P'_k+3[c] with P'[c] taken from lane c's register. The
+      // next panel's chunk takes every pivot first (the look-ahead follows it); the others all of
+      // pivot k, then all of pivot k+1, k+2, k+3, so that two MFMAs on one accumulator sit a
+      // sweep apart. Each element gets the pivots' FMAs in pivot order. The second pair's MFMAs sit
+      // behind the uniform half2 (MFMAs ignore EXEC)
+      if constexpr (c4 < NV) {
+        mfma_chunk<c4>(p0, a0, slot[c4 + 0], slot[c4 + 1], slot[c4 + 2], slot[c4 + 3]);
+        mfma_chunk<c4>(p1, a1, slot[c4 + 0], slot[c4 + 1], slot[c4 + 2], slot[c4 + 3]);
+        if (half2) {
+          mfma_chunk<c4>(p2, a2, slot[c4 + 0], slot[c4 + 1], slot[c4 + 2], slot[c4 + 3]);
+          mfma_chunk<c4>(p3, a3, slot[c4 + 0], slot[c4 + 1], slot[c4 + 2], slot[c4 + 3]);
+          if (c4 < n) look(std::integral_constant<int, c4>{});  // columns k+4, k+5 are final
         }
-        static_for<c2 / 4 + 1, NV / 4>([&](auto JC) {
+      }
+      // (the other chunks: issued below, under the first loads of the J sums)
+      const auto sweep_rest = [&]() {
+        static_for<c4 / 4 + 1, NV / 4>([&](auto JC) {
           constexpr int c = 4 * decltype(JC)::value;
           mfma_chunk<c>(p0, a0, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
         });
-        static_for<c2 / 4 + 1, NV / 4>([&](auto JC) {
+        static_for<c4 / 4 + 1, NV / 4>([&](auto JC) {
           constexpr int c = 4 * decltype(JC)::value;
           mfma_chunk<c>(p1, a1, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
         });
-      }
-      lsync();  // the J sums below read the stored columns
-      // J = L^-T, left-looking, four rows per 16-B read: at k = 0 mod 4 the sums of rows k..k+3
-      // over every finished column j < k (one ds_read_b128 broadcast of P'_j[k..k+3] per column,
-      // four columns per group, the next group's loads issued before this group's FMAs, two
-      // accumulators per row);
-      // rows k, k+1 are finished here, rows k+2, k+3 carry to the next pair step, which adds the
-      // terms of columns k, k+1 (two 8-B reads)
-      if constexpr ((k & 3) == 0) {
+        if (half2) {
+          static_for<c4 / 4 + 1, NV / 4>([&](auto JC) {
+            constexpr int c = 4 * decltype(JC)::value;
+            mfma_chunk<c>(p2, a2, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
+          });
+          static_for<c4 / 4 + 1, NV / 4>([&](auto JC) {
+            constexpr int c = 4 * decltype(JC)::value;
+            mfma_chunk<c>(p3, a3, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
+          });
+        }
+      };
+      // J = L^-T, left-looking, four rows per 16-B read: the sums of rows k..k+3 over every
+      // finished column j < k (one ds_read_b128 broadcast of P'_j[k..k+3] per column, four columns
+      // per group, the next group's loads issued before this group's FMAs, two accumulators per
+      // row); then the triangular solve inside the panel finishes the four rows. The sums read only
+      // earlier panels' columns, so their first loads go out ahead of the sweep's other chunks
+      {
         f2v t0 = {(v == k) ? 1.f : 0.f, 0.f}, t1 = {(v == k1) ? 1.f : 0.f, 0.f};
         f2v t2 = {(v == k + 2) ? 1.f : 0.f, 0.f}, t3 = {(v == k + 3) ? 1.f : 0.f, 0.f};
-        // loads of the next column group issued before this group's FMAs (one group ahead)
-        piped_sweep<0, k, 1>(
+        piped_sweep_under<0, k, 1>(
+            sweep_rest,
             [&](auto C) {
               constexpr int q = decltype(C)::value;  // columns q .. q+3 (4 | k)
               return F4x4{*reinterpret_cast<const float4*>(&sh.P[G::prow(q) + k - q]),
@@ -603,25 +700,22 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
               t0.y = fmaf(slot[q + 3], ld.x, t0.y); t1.y = fmaf(slot[q + 3], ld.y, t1.y);
               t2.y = fmaf(slot[q + 3], ld.z, t2.y); t3.y = fmaf(slot[q + 3], ld.w, t3.y);
             });
-        const float hk = sh.P[G::prow(k) + k1 - (k & ~3)];  // -L[k+1][k]
+        // (rows k+2, k+3 summed here: their FMAs would otherwise sink into the branch below, and
+        // every loaded value stay live down to it)
+        float jc2 = t2.x + t2.y, jc3 = t3.x + t3.y;
+        asm volatile("" : "+v"(jc2), "+v"(jc3));
         const float xk = (t0.x + t0.y) * i0;
         slot[k] = xk;
-        slot[k1] = fmaf(xk, hk, t1.x + t1.y) * i1;
+        slot[k1] = fmaf(xk, hk, t1.x + t1.y) * i1;  // hk = -L[k+1][k]
         xunc = fmaf(slot[k1], g1, fmaf(xk, g0, xunc));
-        jc2 = t2.x + t2.y;
-        jc3 = t3.x + t3.y;
-        asm volatile("" : "+v"(jc2), "+v"(jc3));
-      } else {
-        constexpr int km = k - 2;  // the columns of the pair step before (k - 2 = 0 mod 4)
-        const float2 l0 = *reinterpret_cast<const float2*>(&sh.P[G::prow(km) + k - (km & ~3)]);
-        const float2 l1 = *reinterpret_cast<const float2*>(&sh.P[G::prow(km + 1) + k - (km & ~3)]);
-        const float hk = sh.P[G::prow(k) + k1 - (k & ~3)];
-        const float e0 = fmaf(slot[km + 1], l1.x, fmaf(slot[km], l0.x, jc2));
-        const float e1 = fmaf(slot[km + 1], l1.y, fmaf(slot[km], l0.y, jc3));
-        const float xk = e0 * i0;
-        slot[k] = xk;
-        slot[k1] = fmaf(xk, hk, e1) * i1;
-        xunc = fmaf(slot[k1], g1, fmaf(xk, g0, xunc));
+        if (half2) {  // rows k+2, k+3: the terms of columns k, k+1 on top of their sums
+          const float e0 = fmaf(slot[k1], l12, fmaf(xk, l02, jc2));
+          const float e1 = fmaf(slot[k1], l13, fmaf(xk, l03, jc3));
+          const float xk2 = e0 * i2;
+          slot[k2] = xk2;
+          slot[k3] = fmaf(xk2, hk2, e1) * i3;  // hk2 = -L[k+3][k+2]
+          xunc = fmaf(slot[k3], g3, fmaf(xk2, g2, xunc));
+        }
       }
       pin(slot);
     }
