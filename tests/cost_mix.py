@@ -1,5 +1,6 @@
-"""The per-instance cost mix of tests/test_instance_costs_ref.py and tests/test_gpu_instance_costs.py (a
-helper module, no tests in it).
+"""The per-instance cost mix of tests/test_instance_costs_ref.py and tests/test_gpu_instance_costs.py, and
+what needs both this table and tests/instance_mix.py's: the 16 pairs and the float64 optimum of every
+row of either mix (a helper module, no tests in it).
 
 Four combos of state weights and force regularisation alpha:
 
@@ -11,7 +12,7 @@ every kernel family meets every combo. The records are those of param_sets.CASES
 both tables set, instance i takes model / mu / f_max combo i % 4 of instance_mix and cost combo
 (i // 4) % 4: the 16 pairs.
 
-CPU data of a (case, rotation) is computed once per process and returned read-only.
+CPU data of a (case, rotation, mix) is computed once per process and returned read-only.
 """
 import functools
 
@@ -20,22 +21,19 @@ import numpy as np
 import instance_mix as im
 import model_ref as mr
 import param_sets as ps
+from instance_mix import NC, combo_ids  # noqa: F401  (cx.combo_ids, cx.NC: the same rotation over as many combos)
+from support import package
 
 W2 = (1.0, 0.6, 12, 20, 14, 40, 0.05, 0.02, 0.4, 0.5, 0.35, 0.15)
 
 # combo -> (weights or None for the default, alpha)
 COMBOS = [(None, 4e-5), (ps.W1, 4e-5), (None, 1e-5), (W2, 1e-4)]
-NC = len(COMBOS)
-
-
-def combo_ids(B, s):
-    """Cost combo of each of B instances under rotation s."""
-    return (np.arange(B) + s) % NC
+assert len(COMBOS) == NC
 
 
 def combo_weights(k):
     w = COMBOS[k][0]
-    return tuple(mr._cm().DEFAULT_WEIGHTS) if w is None else tuple(w)
+    return tuple(package().DEFAULT_WEIGHTS) if w is None else tuple(w)
 
 
 def combo_kw(k):
@@ -45,7 +43,12 @@ def combo_kw(k):
 
 def combo_params(k, N, **over):
     """cmpc_params of horizon N with the combo's weights and alpha (everything else the default, or ``over``)."""
-    return mr._cm().make_params(N, **{**combo_kw(k), **over})
+    return package().make_params(N, **{**combo_kw(k), **over})
+
+
+def combo_model(k):
+    """Every cost combo runs the default robot."""
+    return None
 
 
 def combo_rows(ids):
@@ -53,7 +56,7 @@ def combo_rows(ids):
     w = np.array([combo_weights(k) for k in range(NC)], np.float32)
     a = np.array([c[1] for c in COMBOS], np.float32)
     ids = np.asarray(ids)
-    return mr._cm().make_instance_costs(w[ids], a[ids])
+    return package().make_instance_costs(w[ids], a[ids])
 
 
 def table(B, s):
@@ -64,7 +67,7 @@ def table(B, s):
 # ---- both tables: model / mu / f_max combo i % 4 of instance_mix, cost combo (i // 4) % 4 -------------
 def pair_ids(B):
     i = np.arange(B)
-    return i % len(im.COMBOS), (i // 4) % NC
+    return i % im.NC, (i // 4) % NC
 
 
 def pair_params(km, kc, N):
@@ -72,41 +75,42 @@ def pair_params(km, kc, N):
     return combo_params(kc, N, mu=im.COMBOS[km][1], f_max=im.COMBOS[km][2])
 
 
-def fp64_rows(recs, N, cost_ids, model_ids=None, dtype=np.float64):
-    """model_ref.fp64_solve of every record under its own cost combo (and, with model_ids, its own
-    instance_mix combo) -> (x64 [B, 12N], qpOASES returns [B])."""
+def fp64_rows(recs, N, cost_ids=None, model_ids=None, dtype=np.float64):
+    """model_ref.fp64_solve of every record under its own cost combo and its own instance_mix combo
+    (None: combo 0, the defaults, for every record) -> (x64 [B, 12N], qpOASES returns [B])."""
     from concurrent.futures import ThreadPoolExecutor
-    if model_ids is None:
-        model_ids = np.zeros(len(recs), int)
+    cost_ids = np.zeros(len(recs), int) if cost_ids is None else cost_ids
+    model_ids = np.zeros(len(recs), int) if model_ids is None else model_ids
     prms = {(km, kc): pair_params(km, kc, N) for km in set(map(int, model_ids)) for kc in set(map(int, cost_ids))}
-    mdls = [im.combo_model(k) for k in range(len(im.COMBOS))]
+    mdls = [im.combo_model(k) for k in range(im.NC)]
     with ThreadPoolExecutor(8) as ex:
         out = list(ex.map(lambda a: mr.fp64_solve(a[0], prms[(int(a[1]), int(a[2]))], mdls[int(a[1])], dtype),
                           zip(recs, model_ids, cost_ids)))
     return np.array([x for x, _ in out]), np.array([ri for _, ri in out])
 
 
-@functools.lru_cache(maxsize=None)
-def cpu_data(case, s=0):
-    """-> dict(N, recs, ids, x64, ri64) of a case under rotation s: the fp64 optimum of every
-    instance under its own row's weights and alpha."""
+def _cpu_data(case, cost_ids=None, model_ids=None, **ids):
+    """-> the read-only dict(N, recs, **ids, x64, ri64) of a case: the fp64 optimum of every instance
+    under its own row of either table."""
     N = ps.CASES[case][0]
     recs = ps.case_records("default", case)
-    ids = combo_ids(len(recs), s)
-    x64, ri64 = fp64_rows(recs, N, ids)
-    for a in (recs, ids, x64, ri64):
+    x64, ri64 = fp64_rows(recs, N, cost_ids, model_ids)
+    for a in (recs, x64, ri64, *ids.values()):
         a.setflags(write=False)
-    return dict(N=N, recs=recs, ids=ids, x64=x64, ri64=ri64)
+    return dict(N=N, recs=recs, **ids, x64=x64, ri64=ri64)
+
+
+@functools.lru_cache(maxsize=None)
+def cpu_data(case, s=0, mix="cost"):
+    """-> dict(N, recs, ids, x64, ri64) of a case under rotation s of one mix, the other table absent:
+    "cost", each row's own weights and alpha; "model", its own instance_mix model, mu and f_max."""
+    ids = combo_ids(ps.CASES[case][1], s)
+    return _cpu_data(case, ids=ids, **{f"{mix}_ids": ids})
 
 
 @functools.lru_cache(maxsize=None)
 def cpu_data_pairs(case):
     """-> dict(N, recs, mids, cids, x64, ri64) of a case with both tables: the fp64 optimum of every
     instance under its own (model, mu, f_max, cost) pair."""
-    N = ps.CASES[case][0]
-    recs = ps.case_records("default", case)
-    mids, cids = pair_ids(len(recs))
-    x64, ri64 = fp64_rows(recs, N, cids, mids)
-    for a in (recs, mids, cids, x64, ri64):
-        a.setflags(write=False)
-    return dict(N=N, recs=recs, mids=mids, cids=cids, x64=x64, ri64=ri64)
+    mids, cids = pair_ids(ps.CASES[case][1])
+    return _cpu_data(case, cids, mids, mids=mids, cids=cids)

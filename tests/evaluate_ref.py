@@ -99,3 +99,26 @@ def evaluate(orc, rec, prm, U):
     xs, cost, cost0, _ = trajectory(orc, rec, prm, U)
     _, grad = dense(orc, rec, prm, U)
     return xs, certificate(rec, prm, U, grad, cost, cost0)
+
+
+def gap_bound(Hg, rec, prm, U, x64, dist):
+    """An upper bound of the Frank-Wolfe gap of a feasible U that is within ``dist`` (inf-norm, in
+    newtons) of the optimum U* = x64. With d = U - U* and y the gap's maximiser at U,
+      gap(U) = grad(U).(U - y) = grad(U*).(U* - y) + grad(U*).d + d'H(U - y)
+             <= 0 + |d|_inf (|grad(U*)|_1 + |H (U - y)|_1),
+    the first term by U*'s optimality. ``Hg``: the caller's fp64 condensation (qH, qg) of the record,
+    under its own robot model; the stance columns only are used."""
+    N = prm.horizon
+    ub, stance, mui = _consts(rec, prm)
+    keep = np.repeat(stance, 3)
+    H, g = Hg
+    U = np.asarray(U, np.float64)
+    grad = (H @ U + g).reshape(4 * N, 3)
+    mu = 1.0 / mui
+    y = np.zeros((4 * N, 3))
+    lift = stance & (ub * (grad[:, 2] - mu * np.abs(grad[:, 0]) - mu * np.abs(grad[:, 1])) < 0)
+    y[lift, 0] = -np.sign(grad[lift, 0]) * mu * ub[lift]
+    y[lift, 1] = -np.sign(grad[lift, 1]) * mu * ub[lift]
+    y[lift, 2] = ub[lift]
+    g_opt = (H @ x64 + g)[keep]
+    return dist * (np.abs(g_opt).sum() + np.abs((H @ (U - y.reshape(-1)))[keep]).sum())

@@ -10,15 +10,14 @@ oracle: equal at the default model, and the scaling identity under (c m, c I).
 
 A model is a ``cmpc_model`` (``make_model``); MODELS holds the sets of tests/test_gpu_model.py.
 """
-import contextlib
 import functools
-import importlib
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 import evaluate_ref as er
 import param_sets as ps
+from support import package
 
 # name -> (mass, inertia); "mini" (a Mini-Cheetah-sized body) is reported, not gated: condensing in
 # fp32 alone moves its optimum by 1.4e-4 at N = 10 (test_model_ref.test_fp32_condensation_condition)
@@ -34,14 +33,10 @@ GATED = ["heavy", "payload", "x2", "massonly", "iperm"]
 DEFAULT = (12.0, (0.07, 0.26, 0.242))
 
 
-def _cm():
-    return importlib.import_module("quad-periodic-mpc_amd")
-
-
 def model(name):
     """The named set (or "default") as a cmpc_model."""
     m, I = DEFAULT if name == "default" else MODELS[name]
-    return _cm().make_model(m, I)
+    return package().make_model(m, I)
 
 
 def mass_inertia(mdl):
@@ -208,11 +203,3 @@ def evaluate(rec, prm, mdl, U):
 
 def trajectory(rec, prm, mdl, U):
     return er.trajectory(_ModelOracle(mdl), rec, prm, U)
-
-
-@contextlib.contextmanager
-def closing(s):
-    try:
-        yield s
-    finally:
-        s.close()

@@ -10,10 +10,11 @@ CPU data of a (set, case) is computed once per process (inputs, the restated ref
 its default summation order, the float64 optimum of every instance) and returned read-only.
 """
 import functools
-import importlib
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
+
+from support import package, reduced_sizes
 
 W1 = (0.4, 0.25, 8, 10, 2, 50, 0.03, 0.01, 0.3, 0.2, 0.32, 0.1)
 
@@ -48,28 +49,20 @@ CASES = {
 FAMILY_EDGES = [0, 60, 64, 72, 80, 96, 120]
 
 
-def _cm():
-    return importlib.import_module("quad-periodic-mpc_amd")
-
-
 def set_params(name, N, **over):
     """make_params(N) with the named set's values (``over``: further keywords on top)."""
-    return _cm().make_params(N, **{**SETS[name], **over})
+    return package().make_params(N, **{**SETS[name], **over})
 
 
 def case_records(set_name, case):
     """The case's records, their trajectories built with the set's dt."""
-    cm = _cm()
+    cm = package()
     N, B, kw, span = CASES[case]
     recs = cm.make_instances(B, N, dt=SETS[set_name].get("dt", 0.026), **kw)
     n = reduced_sizes(recs, N)
     if span is not None:
         assert n.min() >= span[0] and n.max() <= span[1], (case, int(n.min()), int(n.max()))
     return recs
-
-
-def reduced_sizes(recs, N):
-    return 3 * (_cm().unpack_gait(recs, N) != 0).sum(1)
 
 
 def family_counts(recs, N=10):

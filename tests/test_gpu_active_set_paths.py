@@ -11,11 +11,11 @@ instance generator that empties one of them fails here instead of passing vacuou
 What can be read from the outputs (forces, status, iters), per instance:
   * trips = iters. Every trip is an add or a drop, and the positions at the end are adds - drops, so
     drops = (iters - positions) / 2. The positions are at most the constraints whose slack at the
-    returned forces is within ACT_HI of zero (a loose count that can only be too large), hence
+    returned forces is within support.ACT_HI of zero (a loose count that can only be too large), hence
     iters > that count proves a drop.
   * a solved instance with iters >= 1 ended right after an add (the loop leaves only from the
     selection, which follows an add).
-  * the positions are at least the constraints whose slack is within ACT_LO of zero: an active
+  * the positions are at least the constraints whose slack is within support.ACT_LO of zero: an active
     constraint sits on its plane up to fp32 rounding, and the solver itself only adds a constraint
     violated by more than 1e-5 max(1, |x|_max), so twice that counts none that was merely close
     except in a band of 3e-5 max(1, |x|_max) above zero.
@@ -27,12 +27,11 @@ its counts), the wide classes (n > 72; at N = 12 their refining builds).
 import numpy as np
 import pytest
 
-from test_gpu_parity import assert_failed_reference, assert_parity, gpu_solve, solver_mod  # noqa: F401
+from support import active_counts, gpu_solve, solver_mod  # noqa: F401
+from test_gpu_parity import assert_failed_reference, assert_parity
 
 pytestmark = pytest.mark.gpu
 
-ACT_HI = 1e-3   # slack <= ACT_HI max(1, |f|_max): counted as possibly active (upper count)
-ACT_LO = 2e-5   # slack <= ACT_LO max(1, |f|_max): counted as active (lower count)
 QI = {60: 42, 64: 45}   # positions up to which class 1 keeps R^-1 (SharedC1<NV>::QI)
 
 # (N, stress, batch, seed, size bins (lo, hi] that must be populated, class-1 instance past QI):
@@ -49,23 +48,6 @@ N10_BINS = C1_BINS + ((64, 72), (72, 80), (80, 96))
 BATCHES = [(10, False, 2048, 7304, N10_BINS, False),
            (10, True, 2048, 7300, N10_BINS + ((96, 120),), True),
            (12, False, 1024, 7300, ((72, 80), (80, 96), (96, 120)), False)]
-
-
-def active_counts(cm, prm, recs, f):
-    """Per instance: n, and the upper / lower counts of active constraints at forces f."""
-    N = prm.horizon
-    stance = cm.unpack_gait(recs, N) != 0                      # [B, 4N] per foot-step
-    f3 = np.asarray(f, np.float64).reshape(len(f), 4 * N, 3)
-    fx, fy, fz = f3[..., 0], f3[..., 1], f3[..., 2]
-    mui = 1.0 / prm.mu
-    fn = 1.0 / np.sqrt(mui * mui + 1.0)
-    slack = np.stack([(mui * fx + fz) * fn, (-mui * fx + fz) * fn, (mui * fy + fz) * fn,
-                      (-mui * fy + fz) * fn, fz, prm.f_max - fz], -1)      # [B, 4N, 6]
-    scale = np.maximum(1.0, np.abs(f3).max(axis=(1, 2)))[:, None, None]
-    live = stance[..., None]
-    hi = ((slack <= ACT_HI * scale) & live).sum(axis=(1, 2))
-    lo = ((slack <= ACT_LO * scale) & live).sum(axis=(1, 2))
-    return 3 * stance.sum(1), hi, lo
 
 
 def family_masks(n, hi):

@@ -14,8 +14,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_params, load_golden, rel_force_err
-
-TIGHT = dict(max_iter=10000, rho=1e-3, sigma=1e-8, alpha=1.5, terminate=1e-4)
+from support import TIGHT
 
 
 def test_oracle_admm_reaches_qpoases(cm, orc):

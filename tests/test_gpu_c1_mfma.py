@@ -28,8 +28,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_gpu_active_set_paths import active_counts
-from test_gpu_parity import assert_failed_reference, assert_parity, gpu_solve, solver_mod  # noqa: F401
+from support import active_counts, gpu_solve, solver_mod  # noqa: F401
+from test_gpu_parity import assert_failed_reference, assert_parity
 
 pytestmark = pytest.mark.gpu
 

@@ -14,29 +14,17 @@ smallest at which a panel can go wrong, not the workload's own.
   alpha: the cost table refuses a row with alpha <= 0), the expected status from the smallest
   eigenvalue of the condensation hook's H in float64.
 """
-import importlib
 
 import numpy as np
 import pytest
 
-from test_gpu_c1_static_rows import set_tables
-from test_gpu_parity import assert_parity, gpu_solve
-from status_cases import NOT_PD, OK, bits
+from status_cases import NOT_PD, OK
+from support import bits, gpu_solve, package, reduced_sizes, set_tables, solver_mod  # noqa: F401
+from test_gpu_parity import assert_parity
 
 pytestmark = pytest.mark.gpu
 
 B_LIVE = 192
-
-
-@pytest.fixture(scope="module")
-def solver_mod():
-    mod = importlib.import_module("quad-periodic-mpc_amd.solver")
-    mod.load_library()
-    return mod
-
-
-def _cm():
-    return importlib.import_module("quad-periodic-mpc_amd")
 
 
 def count_tables(rng, N, counts):
@@ -47,12 +35,8 @@ def count_tables(rng, N, counts):
     return tab.reshape(len(counts), N, 4)
 
 
-def reduced_sizes(recs, N):
-    return 3 * (_cm().unpack_gait(recs, N) != 0).sum(1)
-
-
 def counted_records(N, B, seed, counts):
-    recs = _cm().make_instances(B, N, seed=seed, random_contact_frac=0.0)
+    recs = package().make_instances(B, N, seed=seed, random_contact_frac=0.0)
     recs = set_tables(recs, N, count_tables(np.random.default_rng(seed), N, counts))
     assert (reduced_sizes(recs, N) == 3 * np.asarray(counts)).all()
     return recs
@@ -67,7 +51,7 @@ LIVE = [("n0", 1, 0), ("n3", 1, 1), ("n6", 1, 2), ("n9", 1, 3), ("n12", 1, 4),
 
 def live_records(N, fs, seed):
     if fs is None:
-        return _cm().make_instances(B_LIVE, N, seed=seed, random_contact_frac=1.0)
+        return package().make_instances(B_LIVE, N, seed=seed, random_contact_frac=1.0)
     return counted_records(N, B_LIVE, seed, np.full(B_LIVE, fs))
 
 

@@ -14,7 +14,6 @@ step. Every other table takes the exchange through the LDS.
   tests/test_gpu_params.py and tests/test_gpu_model.py hold theirs.
 """
 import functools
-import importlib
 
 import numpy as np
 import pytest
@@ -22,33 +21,15 @@ import pytest
 import model_ref as mr
 import param_sets as ps
 from conftest import rel_force_err
-from test_gpu_parity import COND_BOUND, assert_parity, gpu_solve
+from support import (COND_BOUND, REF_TOL, assert_swing_zero, closing, gpu_solve, package, set_tables,  # noqa: F401
+                     solver_mod)
+from test_gpu_parity import assert_parity
 
 pytestmark = pytest.mark.gpu
 
 HORIZONS = [1, 2, 3, 10]
 B_LIVE = 192
 PAIRS = [(0, 1), (0, 2), (0, 3), (1, 2), (1, 3), (2, 3)]
-REF_TOL = 1e-4     # tests/test_gpu_params.py gate (a)
-
-
-@pytest.fixture(scope="module")
-def solver_mod():
-    mod = importlib.import_module("quad-periodic-mpc_amd.solver")
-    mod.load_library()
-    return mod
-
-
-def _cm():
-    return importlib.import_module("quad-periodic-mpc_amd")
-
-
-def set_tables(recs, N, tab):
-    """Write the stance tables tab [B, N, 4] (0 / 1) into the records' gait words."""
-    off = importlib.import_module("quad-periodic-mpc_amd.records").gait_offset(N)
-    recs = np.ascontiguousarray(recs).copy()
-    recs[:, off:off + N].view(np.uint8)[:, :] = tab.reshape(len(recs), 4 * N).astype(np.uint8)
-    return recs
 
 
 def pair_tables(rng, B, N):
@@ -77,7 +58,7 @@ def near_miss_tables(rng, B, N):
 
 @functools.lru_cache(maxsize=None)
 def live_records(kind, N):
-    cm = _cm()
+    cm = package()
     if kind == "trot":
         recs = cm.make_instances(B_LIVE, N, seed=7000 + N, random_contact_frac=0.0)
     elif kind == "pairs":
@@ -91,7 +72,7 @@ def live_records(kind, N):
 
 
 def stance_counts(recs, N):
-    return (_cm().unpack_gait(recs, N) != 0).reshape(len(recs), N, 4).sum(2)
+    return (package().unpack_gait(recs, N) != 0).reshape(len(recs), N, 4).sum(2)
 
 
 # ---- 1. the hook in row-owner mode ---------------------------------------------------------------
@@ -191,11 +172,6 @@ def test_one_record_every_build(cm, solver_mod):
 
 
 # ---- 4. non-default parameters and model ---------------------------------------------------------
-def assert_swing_zero(cm, recs, N, f):
-    swing = np.repeat(cm.unpack_gait(recs, N) == 0, 3, axis=1)
-    assert np.all(f[swing] == 0.0)
-
-
 @pytest.mark.parametrize("set_name", ps.NON_DEFAULT)
 def test_trot_under_set(cm, orc, solver_mod, set_name):
     """The N = 10 trot batch of test_live_parity (192 instances, every phase table; trajectories
@@ -242,7 +218,7 @@ def test_trot_under_model(cm, orc, solver_mod):
     assert len({t.tobytes() for t in cm.unpack_gait(recs, N)}) == 18
     x64, ri64 = mr.fp64_batch(recs, prm, mdl)
     assert (ri64 == 0).all()
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=len(recs), model=mdl)) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=len(recs), model=mdl)) as s:
         f, st, _ = s.solve_host(recs)
     e64 = ps.rel_dist(f, x64)
     print(f"[c1-static-rows] model heavy: ours within {e64.max():.1e} of the fp64 optimum")

@@ -11,21 +11,14 @@ per horizon step and two FMAs per entry instead of a 13-term dot product with a 
   with mostly padding lanes;
 * one refining wide build (N = 12 all-stance, n = 144).
 """
-import importlib
 
 import numpy as np
 import pytest
 
-from test_gpu_parity import COND_BOUND, assert_failed_reference, assert_parity, gpu_solve
+from support import COND_BOUND, gpu_solve, solver_mod  # noqa: F401
+from test_gpu_parity import assert_failed_reference, assert_parity
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def solver_mod():
-    mod = importlib.import_module("quad-periodic-mpc_amd.solver")
-    mod.load_library()
-    return mod
 
 
 @pytest.mark.parametrize("N", [1, 2, 3, 10])

@@ -13,7 +13,6 @@ bench.py --config 4 times.
 """
 import importlib
 import os
-import socket
 import sys
 
 import numpy as np
@@ -21,6 +20,7 @@ import pytest
 import torch
 
 from conftest import ROOT, rel_force_err
+from support import free_port
 
 pytestmark = pytest.mark.gpu
 
@@ -91,14 +91,6 @@ def _pipeline_world1(par, prm, recs_dev):
     return f_pipe, st_pipe
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def _worker(rank, world, port, out_path, q):
     try:
         sys.path.insert(0, ROOT)
@@ -143,7 +135,7 @@ def test_root_pipeline_world2_gloo_real_solve(config4, tmp_path):
     out_path = str(tmp_path / "f_world2.npy")
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, world, port, out_path, q)) for r in range(world)]
     for p in procs:
         p.start()

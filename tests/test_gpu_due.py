@@ -14,100 +14,23 @@ import importlib
 import numpy as np
 import pytest
 
+from support import (ST_FILL, Dev, assert_due_result, bits, full_solve, package, records, reduced_sizes,  # noqa: F401
+                     sentinel_forces, solver, solver_mod)
+
 pytestmark = pytest.mark.gpu
 
 # reduced sizes on both sides of every class edge (tests/test_gpu_parity.py CLASS_EDGES: 60, 64, 80,
 # 96, 120, 128, 144, 192) and of the tail class's 72
 TARGETS = [3, 57, 60, 63, 66, 72, 75, 81, 96, 99, 120, 123, 129, 144, 147, 192, 195, 240]
 EDGES = [0, 60, 64, 72, 80, 96, 120, 128, 144, 192, 256]
-ST_FILL, IT_FILL = 0xAB, -7
-
-
-@pytest.fixture(scope="module")
-def solver_mod():
-    mod = importlib.import_module("quad-periodic-mpc_amd.solver")
-    mod.load_library()
-    return mod
-
-
-def _R():
-    return importlib.import_module("quad-periodic-mpc_amd.records")
-
-
-def bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def sentinel_forces(B, cols):
-    """A distinct finite float per word (2^23 + index), so a stray write shows wherever it lands."""
-    return (np.uint32(0x4B000000) + np.arange(B * cols, dtype=np.uint32)).view(np.float32).reshape(B, cols)
-
-
-def reduced_sizes(recs, N):
-    """n = 3 x stance foot-steps per record (gait byte x f_max = 120 N: any nonzero byte)."""
-    return 3 * (_R().unpack_gait(recs, N) != 0).sum(1)
-
-
-class Dev:
-    """One handle plus the device buffers of a batch; every call synchronises (the handle runs on
-    its own stream, the uploads on torch's)."""
-
-    def __init__(self, solver_mod, prm, B, refine=True, out_steps=0):
-        import torch
-        self.torch, self.B = torch, B
-        self.s = solver_mod.BatchSolver(prm, max_batch=B)
-        if not refine:
-            self.s.set_refine(False)
-        if out_steps:
-            self.s.set_output_steps(out_steps)
-        self.cols = self.s.out_cols
-
-    def close(self):
-        self.s.close()
-
-    def run(self, recs, due=None):
-        """Pre-fill the outputs with the sentinels, solve, -> (forces, status, iters) as numpy."""
-        torch = self.torch
-        r = torch.from_numpy(np.array(recs, np.float32)).cuda()
-        f = torch.from_numpy(sentinel_forces(self.B, self.cols)).cuda()
-        st = torch.full((self.B,), ST_FILL, dtype=torch.uint8, device="cuda")
-        it = torch.full((self.B,), IT_FILL, dtype=torch.int32, device="cuda")
-        d = None if due is None else torch.from_numpy(np.array(due, np.uint8)).cuda()
-        torch.cuda.synchronize()
-        self.s.solve(r, f, st, it, due=d)
-        torch.cuda.synchronize()  # returns: the handle's stream drained
-        return f.cpu().numpy(), st.cpu().numpy(), it.cpu().numpy()
-
-
-def full_solve(solver_mod, prm, recs, **kw):
-    d = Dev(solver_mod, prm, recs.shape[0], **kw)
-    try:
-        return d.run(recs)
-    finally:
-        d.close()
-
-
-def assert_due_result(got, ref, due, cols):
-    """Due rows carry the unmasked solve's bits, the others their sentinels."""
-    f, st, it = got
-    f_ref, st_ref, it_ref = ref
-    m = np.asarray(due) != 0
-    sent = sentinel_forces(len(m), cols)
-    assert (st_ref <= 4).all() and (it_ref >= 0).all()   # the comparator wrote every row
-    np.testing.assert_array_equal(bits(f)[m], bits(f_ref)[m])
-    np.testing.assert_array_equal(st[m], st_ref[m])
-    np.testing.assert_array_equal(it[m], it_ref[m])
-    np.testing.assert_array_equal(bits(f)[~m], bits(sent)[~m])
-    assert (st[~m] == ST_FILL).all() and (it[~m] == IT_FILL).all()
 
 
 @functools.lru_cache(maxsize=None)
 def class_batch(N):
     """Four instances per reduced size of TARGETS (two of them due) + 12 random ones, the last of
     the batch due -> (records, due)."""
-    cm = importlib.import_module("quad-periodic-mpc_amd")
-    R = _R()
+    cm = package()
+    R = records()
     targets = [t for t in TARGETS if t <= 12 * N]
     B = 4 * len(targets) + 12
     B += B % 64 == 0                              # (N = 11: 52 + 12) never a multiple of the wavefront
@@ -137,10 +60,8 @@ CASES = [(3, True, 0), (10, True, 0), (11, True, 0), (16, True, 0), (20, True, 0
 
 @functools.lru_cache(maxsize=None)
 def class_batch_reference(N, refine, out_steps):
-    solver_mod = importlib.import_module("quad-periodic-mpc_amd.solver")
-    cm = importlib.import_module("quad-periodic-mpc_amd")
     recs, _ = class_batch(N)
-    return full_solve(solver_mod, cm.make_params(N), recs, refine=refine, out_steps=out_steps)
+    return full_solve(solver(), package().make_params(N), recs, refine=refine, out_steps=out_steps)
 
 
 @pytest.mark.parametrize("N,refine,out_steps", CASES)
@@ -165,7 +86,7 @@ def test_not_due_records_are_never_read(cm, solver_mod, N):
     """Every word of the records that are not due is a NaN pattern and their gait bytes 0xFF (a
     reduced size of 12 N if it were counted): the outputs are bit-identical to the clean batch's."""
     recs, due = class_batch(N)
-    R = _R()
+    R = records()
     bad = recs.copy()
     nd = due == 0
     bad.view(np.uint32)[nd] = 0x7FC00000
@@ -220,12 +141,11 @@ def test_degenerate_masks(cm, solver_mod, N):
 
 @functools.lru_cache(maxsize=None)
 def large_batch(N):
-    cm = importlib.import_module("quad-periodic-mpc_amd")
-    solver_mod = importlib.import_module("quad-periodic-mpc_amd.solver")
+    cm = package()
     B = 16384
     recs = cm.make_instances(B, N, seed=6300 + N, random_contact_frac=1.0)
     recs.setflags(write=False)
-    return recs, full_solve(solver_mod, cm.make_params(N), recs)
+    return recs, full_solve(solver(), cm.make_params(N), recs)
 
 
 @pytest.mark.parametrize("pre_trot", [False, True])
@@ -262,7 +182,7 @@ def test_estimator_due(cm, solver_mod, source):
     after the first call the due instances equal the unmasked step of a copy and the others their
     state before it; after the second every instance equals the unmasked step."""
     import torch
-    R = _R()
+    R = records()
     N, B = 20, 6
     counts = [399, 400, 450, 500, 501, 0]
     prm = cm.make_params(N)
@@ -323,7 +243,7 @@ def test_staggered_closed_loop(cm, solver_mod):
     merged into the held forces and status -> rollout(due). Controller state, held forces and
     status are bit-identical after every tick."""
     import torch
-    R = _R()
+    R = records()
     inst = importlib.import_module("quad-periodic-mpc_amd.instances")
     N, B, ITERS, DT = 10, 256, 13, 0.002
     ticks = 3 * ITERS + 2

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_params, load_golden, rel_force_err
+from support import solver_mod  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -26,13 +27,6 @@ def on_stream():
     with torch.cuda.stream(st):
         yield st
     torch.cuda.synchronize()
-
-
-@pytest.fixture(scope="module")
-def solver_mod():
-    mod = importlib.import_module("quad-periodic-mpc_amd.solver")
-    mod.load_library()
-    return mod
 
 
 def _run_sequence(torch, s, g, B):

@@ -17,6 +17,7 @@ import pytest
 import evaluate_ref as er
 import param_sets
 from conftest import golden_params, load_golden
+from support import solver_mod  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -28,14 +29,6 @@ CASES = ["n1", "n2", "n10_edge", "n11", "n20_mixed", "n20_standing"]
 # tests/param_sets.py (twelve distinct non-zero weights; mu, f_max, alpha and dt all moved), so a
 # wrong weight index or coefficient in the kernel's closed forms shows; the bars are the same
 CASES += [f"{c}@{s}" for s in ("W1", "all") for c in ("n2", "n10_edge", "n20_mixed")]
-
-
-@pytest.fixture(scope="module")
-def solver_mod():
-    import importlib
-    mod = importlib.import_module("quad-periodic-mpc_amd.solver")
-    mod.load_library()
-    return mod
 
 
 def _stance(cm, prm, rec):

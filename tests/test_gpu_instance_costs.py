@@ -30,104 +30,30 @@ import pytest
 
 import cost_mix as cx
 import instance_mix as im
-import model_ref as mr
 import param_sets as ps
-from test_gpu_due import ST_FILL, IT_FILL, bits, sentinel_forces
+import support
+from support import (FP64_TOL, IT_FILL, REF_TOL, ST_FILL, TIGHT, assert_same_bits, bits, closing, half_due,  # noqa: F401
+                     nan_where_not_due, package, records, row_by_row, rows_of, sentinel_forces, sentinel_solve,
+                     solver, solver_mod)
 
 pytestmark = pytest.mark.gpu
 
-REF_TOL = 1e-4    # N <= 10: ours against the fp64 optimum
-FP64_TOL = 1e-5   # N >= 11 (refined)
 NC = cx.NC
+shared = functools.partial(support.shared_handle, cx)   # (k, N, B): a fresh shared handle of cost combo k
+shared_solve = functools.partial(support.shared_solve, cx)   # (k, case): its solve of the whole batch, cached
+rowwise = functools.partial(support.rowwise, cx)   # (case, ids): row i of the shared handle of cost combo ids[i]
 BAD_INPUT = 4     # CMPC_BAD_INPUT
-
-
-@pytest.fixture(scope="module")
-def solver_mod():
-    mod = importlib.import_module("quad-periodic-mpc_amd.solver")
-    mod.load_library()
-    return mod
-
-
-def _smod():
-    return importlib.import_module("quad-periodic-mpc_amd.solver")
-
-
-def _cm():
-    return importlib.import_module("quad-periodic-mpc_amd")
-
-
-def run(s, recs, due=None):
-    """One device solve into sentinel-filled buffers -> (forces, status, iters)."""
-    import torch
-    B, oc = recs.shape[0], s.out_cols
-    r = torch.from_numpy(np.array(recs, np.float32)).cuda()
-    f = torch.from_numpy(sentinel_forces(B, oc)).cuda()
-    st = torch.full((B,), ST_FILL, dtype=torch.uint8, device="cuda")
-    it = torch.full((B,), IT_FILL, dtype=torch.int32, device="cuda")
-    dd = None if due is None else torch.from_numpy(np.array(due, np.uint8)).cuda()
-    torch.cuda.synchronize()
-    s.solve(r, f, st, it, due=dd)
-    torch.cuda.synchronize()
-    return f.cpu().numpy(), st.cpu().numpy(), it.cpu().numpy()
-
-
-def assert_same_bits(got, want, msg=""):
-    for a, b in zip(got, want):
-        np.testing.assert_array_equal(bits(a), bits(b), err_msg=msg)
-
-
-def shared(k, N, B):
-    """A fresh shared handle of cost combo k (default robot, mu 0.4, f_max 120)."""
-    return _smod().BatchSolver(cx.combo_params(k, N), max_batch=B)
 
 
 def cost_handle(N, B, tab):
     """A default handle (default weights, alpha 4e-5) with the cost table set."""
-    s = _smod().BatchSolver(_cm().make_params(N), max_batch=B)
+    s = solver().BatchSolver(package().make_params(N), max_batch=B)
     try:
         s.set_instance_costs(tab)
     except Exception:
         s.close()
         raise
     return s
-
-
-def half_due(B, seed=5):
-    due = np.zeros(B, np.uint8)
-    due[np.random.default_rng(seed).choice(B, B // 2, replace=False)] = 1
-    return due
-
-
-def nan_where_not_due(recs, due):
-    out = np.array(recs, np.float32)
-    out[due == 0] = np.nan
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def shared_solve(k, case):
-    """(forces, status, iters) of the case's whole batch on the shared handle of cost combo k; once per process."""
-    N = ps.CASES[case][0]
-    recs = ps.case_records("default", case)
-    with mr.closing(shared(k, N, len(recs))) as s:
-        out = run(s, recs)
-    for a in out:
-        a.setflags(write=False)
-    return out
-
-
-def rowwise(case, ids):
-    """Row i of the shared handle of cost combo ids[i]."""
-    outs = [shared_solve(k, case) for k in range(NC)]
-    return tuple(np.stack([outs[k][j][i] for i, k in enumerate(ids)]) for j in range(3))
-
-
-def _rows_of(outs, ids):
-    """outs[k]: an array (or tuple of arrays) of combo k's shared handle -> row i from combo ids[i]."""
-    if isinstance(outs[0], tuple):
-        return tuple(_rows_of([o[j] for o in outs], ids) for j in range(len(outs[0])))
-    return np.stack([outs[k][i] for i, k in enumerate(ids)])
 
 
 # ---- 1: a uniform table is the shared handle ---------------------------------------------------------
@@ -140,17 +66,17 @@ def test_uniform_table_is_the_shared_handle(cm, solver_mod, case, k, masked):
     B = len(recs)
     due = half_due(B) if masked else None
     rin = nan_where_not_due(recs, due) if masked else recs
-    with mr.closing(shared(k, N, B)) as s:
-        want = run(s, rin, due)
+    with closing(shared(k, N, B)) as s:
+        want = sentinel_solve(s, rin, due)
         assert s.instance_cost_count() == 0
     m = np.ones(B, bool) if due is None else due != 0
     assert (want[1][m] == 0).mean() > 0.9 and (want[1][~m] == ST_FILL).all()
     np.testing.assert_array_equal(bits(want[0][~m]), bits(sentinel_forces(B, 12 * N)[~m]))
-    with mr.closing(cost_handle(N, B, cx.combo_rows(np.full(B, k)))) as s:
+    with closing(cost_handle(N, B, cx.combo_rows(np.full(B, k)))) as s:
         assert s.instance_cost_count() == B and s.instance_count == 0
-        assert_same_bits(run(s, rin, due), want, f"uniform table of cost combo {k}")
-    with mr.closing(solver_mod.BatchSolver(cm.make_params(N), max_batch=B)) as s:
-        assert not np.array_equal(bits(run(s, rin, due)[0])[m], bits(want[0])[m])   # combo k is not the default
+        assert_same_bits(sentinel_solve(s, rin, due), want, f"uniform table of cost combo {k}")
+    with closing(solver_mod.BatchSolver(cm.make_params(N), max_batch=B)) as s:
+        assert not np.array_equal(bits(sentinel_solve(s, rin, due)[0])[m], bits(want[0])[m])   # combo k is not the default
 
 
 # ---- 2: the mixed table, row by row -----------------------------------------------------------------
@@ -165,8 +91,8 @@ def test_mixed_table_row_by_row(cm, solver_mod, case, s_rot):
         counts = ps.family_counts(recs)
         assert min(counts) > 0, counts   # c1-60, c1-64, tail, w80, w96, w120
     want = rowwise(case, ids)
-    with mr.closing(cost_handle(N, B, cx.table(B, s_rot))) as s:
-        got = run(s, recs)
+    with closing(cost_handle(N, B, cx.table(B, s_rot))) as s:
+        got = sentinel_solve(s, recs)
     assert_same_bits(got, want, f"{case} rotation {s_rot}")
     assert (got[1] == 0).mean() > 0.9
     dflt = shared_solve(0, case)
@@ -184,8 +110,8 @@ def test_mixed_table_under_a_due_mask(cm, solver_mod, case, s_rot):
     due = half_due(B, seed=7 + s_rot)
     m = due != 0
     want = rowwise(case, ids)
-    with mr.closing(cost_handle(N, B, cx.table(B, s_rot))) as s:
-        got = run(s, nan_where_not_due(recs, due), due)
+    with closing(cost_handle(N, B, cx.table(B, s_rot))) as s:
+        got = sentinel_solve(s, nan_where_not_due(recs, due), due)
     for g, w in zip(got, want):
         np.testing.assert_array_equal(bits(g[m]), bits(w[m]))   # row i is row i of the table, mask or not
     np.testing.assert_array_equal(bits(got[0][~m]), bits(sentinel_forces(B, 12 * N)[~m]))
@@ -201,8 +127,8 @@ def test_mixed_table_against_the_fp64_optimum(cm, orc, solver_mod, case):
     d = cx.cpu_data(case, 0)
     N, recs, ids, x64 = d["N"], d["recs"], d["ids"], d["x64"]
     assert (d["ri64"] == 0).all(), d["ri64"]
-    with mr.closing(cost_handle(N, len(recs), cx.table(len(recs), 0))) as s:
-        f, st, it = run(s, recs)
+    with closing(cost_handle(N, len(recs), cx.table(len(recs), 0))) as s:
+        f, st, it = sentinel_solve(s, recs)
     e64 = ps.rel_dist(f, x64)
     per = [float(e64[ids == k].max()) for k in range(NC)]
     print(f"[cost] {case}: {len(recs)} instances under the mix, ours within {e64.max():.1e} of the fp64 optimum "
@@ -220,9 +146,9 @@ def pair_solve(km, kc, case):
     """The case's whole batch on the shared handle of the pair (instance_mix combo km, cost combo kc)."""
     N = ps.CASES[case][0]
     recs = ps.case_records("default", case)
-    with mr.closing(_smod().BatchSolver(cx.pair_params(km, kc, N), max_batch=len(recs),
+    with closing(solver().BatchSolver(cx.pair_params(km, kc, N), max_batch=len(recs),
                                         model=im.combo_model(km))) as s:
-        out = run(s, recs)
+        out = sentinel_solve(s, recs)
     for a in out:
         a.setflags(write=False)
     return out
@@ -237,7 +163,7 @@ def test_both_tables_row_by_row(cm, solver_mod, case, order):
     mids, cids = cx.pair_ids(B)
     want = tuple(np.stack([pair_solve(int(km), int(kc), case)[j][i] for i, (km, kc) in enumerate(zip(mids, cids))])
                  for j in range(3))
-    with mr.closing(solver_mod.BatchSolver(cm.make_params(N), max_batch=B)) as s:
+    with closing(solver_mod.BatchSolver(cm.make_params(N), max_batch=B)) as s:
         if order == "params_first":
             s.set_instance_params(im.combo_rows(mids))
             s.set_instance_costs(cx.combo_rows(cids))
@@ -245,7 +171,7 @@ def test_both_tables_row_by_row(cm, solver_mod, case, order):
             s.set_instance_costs(cx.combo_rows(cids))
             s.set_instance_params(im.combo_rows(mids))
         assert s.instance_count == B and s.instance_cost_count() == B
-        got = run(s, recs)
+        got = sentinel_solve(s, recs)
     assert_same_bits(got, want, f"{case}, both tables ({order})")
     assert (got[1] == 0).mean() > 0.9
 
@@ -259,10 +185,10 @@ def test_both_tables_against_the_fp64_optimum(cm, orc, solver_mod, case):
     N, recs, x64 = d["N"], d["recs"], d["x64"]
     B = len(recs)
     assert (d["ri64"] == 0).all(), d["ri64"]
-    with mr.closing(solver_mod.BatchSolver(cm.make_params(N), max_batch=B)) as s:
+    with closing(solver_mod.BatchSolver(cm.make_params(N), max_batch=B)) as s:
         s.set_instance_params(im.combo_rows(d["mids"]))
         s.set_instance_costs(cx.combo_rows(d["cids"]))
-        f, st, it = run(s, recs)
+        f, st, it = sentinel_solve(s, recs)
     e64 = ps.rel_dist(f, x64)
     print(f"[cost] {case}, both tables: ours within {e64.max():.1e} of the fp64 optimum "
           f"(instance {int(e64.argmax())}: model combo {int(d['mids'][e64.argmax()])}, cost combo "
@@ -282,11 +208,11 @@ def test_launch_forms_agree_under_the_mix(cm, solver_mod, N):
     prm = cm.make_params(N)
     recs = cm.make_instances(B, N, seed=8500 + N, random_contact_frac=1.0)
     tab = cx.table(B, 1)
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=B)) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=B)) as s:
         s.set_instance_costs(tab)
         f_all, st_all, it_all = s.solve_host(recs)
     parts = []
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=P)) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=P)) as s:
         for a in range(0, B, P):
             s.set_instance_costs(tab[a:a + P])
             parts.append(s.solve_host(recs[a:a + P]))
@@ -294,7 +220,7 @@ def test_launch_forms_agree_under_the_mix(cm, solver_mod, N):
     diff = np.nonzero((bits(f_p) != bits(f_all)).any(1) | (st_p != st_all) | (it_p != it_all))[0]
     assert diff.size == 0, (diff.size, diff[:8])
     assert (st_all == 0).mean() > 0.99
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=P)) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=P)) as s:
         f_def = s.solve_host(recs[:P])[0]
     ids = cx.combo_ids(P, 1)
     same = (bits(f_def) == bits(f_all[:P])).all(1)
@@ -311,24 +237,24 @@ def test_clear_and_survive(cm, solver_mod):
     tab = cx.table(B, 2)
     want10 = rowwise("n10_families", cx.combo_ids(B, 2))
     want16 = rowwise("n16_trot", cx.combo_ids(len(recs16), 2))
-    with mr.closing(solver_mod.BatchSolver(p10, max_batch=B)) as s:
-        fresh = run(s, recs10)
+    with closing(solver_mod.BatchSolver(p10, max_batch=B)) as s:
+        fresh = sentinel_solve(s, recs10)
         s.set_instance_costs(tab)
         assert s.instance_cost_count() == B
-        assert_same_bits(run(s, recs10), want10, "table set")
+        assert_same_bits(sentinel_solve(s, recs10), want10, "table set")
         s.set_params(p16)                                  # the table survives set_params
         assert s.instance_cost_count() == B
-        assert_same_bits(run(s, recs16), want16, "N = 16 under the same table")
+        assert_same_bits(sentinel_solve(s, recs16), want16, "N = 16 under the same table")
         s.set_params(cx.combo_params(3, 10))               # shared weights and alpha stay hidden
-        assert_same_bits(run(s, recs10), want10, "back at N = 10")
+        assert_same_bits(sentinel_solve(s, recs10), want10, "back at N = 10")
         s.set_params(p10)
         s.set_instance_costs(None)                         # clear: a fresh handle's bits
         assert s.instance_cost_count() == 0
-        assert_same_bits(run(s, recs10), fresh, "cleared")
+        assert_same_bits(sentinel_solve(s, recs10), fresh, "cleared")
         s.set_params(cx.combo_params(1, 10))
         s.set_instance_costs(tab)
         s.set_instance_costs(None)                         # what was set under the table shows again
-        assert_same_bits(run(s, recs10), shared_solve(1, "n10_families"), "shared values after a clear")
+        assert_same_bits(sentinel_solve(s, recs10), shared_solve(1, "n10_families"), "shared values after a clear")
 
 
 def test_new_shared_values_reach_every_row_of_a_cost_table(cm, solver_mod):
@@ -339,18 +265,18 @@ def test_new_shared_values_reach_every_row_of_a_cost_table(cm, solver_mod):
     cids = cx.combo_ids(B, 1)
     km = 1                                                 # instance_mix "heavy", mu 0.6, f_max 150
     want = tuple(np.stack([pair_solve(km, int(kc), case)[j][i] for i, kc in enumerate(cids)]) for j in range(3))
-    with mr.closing(cost_handle(10, B, cx.table(B, 1))) as s:
-        before = run(s, recs)
+    with closing(cost_handle(10, B, cx.table(B, 1))) as s:
+        before = sentinel_solve(s, recs)
         assert_same_bits(before, rowwise(case, cids), "default robot under the cost table")
         s.set_model(im.combo_model(km))
         s.set_params(im.combo_params(km, 10))              # (its weights and alpha, the defaults, stay hidden)
         assert s.instance_cost_count() == B and s.instance_count == 0
-        got = run(s, recs)
+        got = sentinel_solve(s, recs)
         assert_same_bits(got, want, "new model, mu and f_max under the cost table")
         assert not np.array_equal(bits(got[0]), bits(before[0]))
         s.set_model(None)
         s.set_params(cm.make_params(10))
-        assert_same_bits(run(s, recs), before, "and back")
+        assert_same_bits(sentinel_solve(s, recs), before, "and back")
 
 
 def test_new_shared_weights_reach_every_row_of_a_parameter_table(cm, solver_mod):
@@ -361,15 +287,15 @@ def test_new_shared_weights_reach_every_row_of_a_parameter_table(cm, solver_mod)
     mids = im.combo_ids(B, 0)
     kc = 3
     want = tuple(np.stack([pair_solve(int(km), kc, case)[j][i] for i, km in enumerate(mids)]) for j in range(3))
-    with mr.closing(solver_mod.BatchSolver(cm.make_params(10), max_batch=B, instance_params=im.table(B, 0))) as s:
-        before = run(s, recs)
+    with closing(solver_mod.BatchSolver(cm.make_params(10), max_batch=B, instance_params=im.table(B, 0))) as s:
+        before = sentinel_solve(s, recs)
         s.set_params(cx.combo_params(kc, 10))
         assert s.instance_count == B and s.instance_cost_count() == 0
-        got = run(s, recs)
+        got = sentinel_solve(s, recs)
         assert_same_bits(got, want, "new shared weights and alpha under the parameter table")
         assert not np.array_equal(bits(got[0]), bits(before[0]))
         s.set_params(cm.make_params(10))
-        assert_same_bits(run(s, recs), before, "and back")
+        assert_same_bits(sentinel_solve(s, recs), before, "and back")
 
 
 def test_tables_are_cleared_independently(cm, solver_mod):
@@ -381,30 +307,30 @@ def test_tables_are_cleared_independently(cm, solver_mod):
                  for j in range(3))
     only_cost = rowwise(case, cids)
     only_par = tuple(np.stack([pair_solve(int(km), 0, case)[j][i] for i, km in enumerate(mids)]) for j in range(3))
-    with mr.closing(solver_mod.BatchSolver(cm.make_params(10), max_batch=B)) as s:
-        fresh = run(s, recs)
+    with closing(solver_mod.BatchSolver(cm.make_params(10), max_batch=B)) as s:
+        fresh = sentinel_solve(s, recs)
         s.set_instance_costs(cx.combo_rows(cids))
         s.set_instance_params(im.combo_rows(mids))
-        assert_same_bits(run(s, recs), both, "both")
+        assert_same_bits(sentinel_solve(s, recs), both, "both")
         s.set_instance_params(None)                        # the cost table stays
         assert (s.instance_count, s.instance_cost_count()) == (0, B)
-        assert_same_bits(run(s, recs), only_cost, "parameter table cleared")
+        assert_same_bits(sentinel_solve(s, recs), only_cost, "parameter table cleared")
         s.set_instance_params(im.combo_rows(mids))
         s.set_instance_costs(None)                         # the parameter table stays
         assert (s.instance_count, s.instance_cost_count()) == (B, 0)
-        assert_same_bits(run(s, recs), only_par, "cost table cleared")
+        assert_same_bits(sentinel_solve(s, recs), only_par, "cost table cleared")
         s.set_instance_costs(cx.combo_rows(cids))
-        assert_same_bits(run(s, recs), both, "both again")
+        assert_same_bits(sentinel_solve(s, recs), both, "both again")
         s.set_instance_costs(None)
         s.set_instance_params(None)
-        assert_same_bits(run(s, recs), fresh, "neither")
+        assert_same_bits(sentinel_solve(s, recs), fresh, "neither")
 
 
 def test_batch_beyond_either_table_is_refused(cm, solver_mod):
     import torch
     recs = ps.case_records("default", "n3_padding")
     B = len(recs)
-    with mr.closing(solver_mod.BatchSolver(cm.make_params(3), max_batch=B)) as s:
+    with closing(solver_mod.BatchSolver(cm.make_params(3), max_batch=B)) as s:
         r = torch.from_numpy(np.array(recs)).cuda()
         f = torch.from_numpy(sentinel_forces(B, 36)).cuda()
         st = torch.full((B,), ST_FILL, dtype=torch.uint8, device="cuda")
@@ -458,37 +384,37 @@ def test_a_bad_row_is_rejected(cm, solver_mod, kind):
     recs = ps.case_records("default", "n3_padding")
     B = len(recs)
     word, val = BAD[kind]
-    with mr.closing(solver_mod.BatchSolver(cm.make_params(3), max_batch=B)) as s:
-        fresh = run(s, recs)
+    with closing(solver_mod.BatchSolver(cm.make_params(3), max_batch=B)) as s:
+        fresh = sentinel_solve(s, recs)
         t = cx.table(B, 1)
         t[B // 2, word] = val
         with pytest.raises(solver_mod.CmpcError, match=r"\(-2\)"):   # no table yet: none afterwards
             s.set_instance_costs(t)
         assert s.instance_cost_count() == 0
-        assert_same_bits(run(s, recs), fresh, "a rejected first table")
+        assert_same_bits(sentinel_solve(s, recs), fresh, "a rejected first table")
         s.set_instance_costs(cx.table(B, 1))
-        want = run(s, recs)
+        want = sentinel_solve(s, recs)
         assert not np.array_equal(bits(want[0]), bits(fresh[0]))
         t = cx.table(B, 2)
         t[B // 2, word] = val
         with pytest.raises(solver_mod.CmpcError, match=r"\(-2\)"):
             s.set_instance_costs(t)
         assert s.instance_cost_count() == B
-        assert_same_bits(run(s, recs), want, "after a rejected table")
+        assert_same_bits(sentinel_solve(s, recs), want, "after a rejected table")
 
 
 def test_reserved_words_are_not_read(cm, solver_mod):
     recs = ps.case_records("default", "n3_padding")
     B = len(recs)
     t = cx.table(B, 1)
-    with mr.closing(cost_handle(3, B, t)) as s:
-        want = run(s, recs)
+    with closing(cost_handle(3, B, t)) as s:
+        want = sentinel_solve(s, recs)
         t2 = t.copy()
         t2[:, 13:] = np.nan
         t2[B // 2, 13:] = np.float32([np.inf, -1.0, -np.inf])
         s.set_instance_costs(t2)
         assert s.instance_cost_count() == B
-        assert_same_bits(run(s, recs), want, "NaN in the reserved words")
+        assert_same_bits(sentinel_solve(s, recs), want, "NaN in the reserved words")
 
 
 # ---- 8: a degenerate cost ----------------------------------------------------------------------------
@@ -514,8 +440,8 @@ def test_zero_weights_give_zero_forces(cm, solver_mod, case):
     tab = cx.table(B, 0)
     tab[hit, :12] = 0.0
     tab[hit, 12] = 4e-5
-    with mr.closing(cost_handle(N, B, tab)) as s:
-        f, st, it = run(s, recs)
+    with closing(cost_handle(N, B, tab)) as s:
+        f, st, it = sentinel_solve(s, recs)
     keep = np.ones(B, bool)
     keep[hit] = False
     neg = {i: int((bits(f[i]) == 0x80000000).sum()) for i in hit}
@@ -532,13 +458,8 @@ def test_evaluate_row_by_row(cm, solver_mod, case, k):
     recs = ps.case_records("default", case)[:k]
     ids = cx.combo_ids(k, 1)
     f = rowwise(case, cx.combo_ids(len(ps.case_records("default", case)), 1))[0][:k]
-    outs = []
-    for c in range(NC):
-        with mr.closing(shared(c, N, k)) as s:
-            outs.append(s.evaluate_host(recs, f))
-    want = _rows_of(outs, ids)
-    with mr.closing(cost_handle(N, k, cx.table(k, 1))) as s:
-        got = s.evaluate_host(recs, f)
+    got, want, outs = row_by_row(lambda s: s.evaluate_host(recs, f), lambda c: shared(c, N, k),
+                                 lambda: cost_handle(N, k, cx.table(k, 1)), ids, NC)
     np.testing.assert_array_equal(bits(got[0]), bits(want[0]))                       # x_pred
     np.testing.assert_array_equal(got[1].view(np.uint64), want[1].view(np.uint64))   # all eight words
     assert not np.array_equal(got[1][ids != 0], outs[0][1][ids != 0])
@@ -561,20 +482,14 @@ def test_condense_row_by_row(cm, solver_mod, N, rows):
     B = 8
     recs = torch.from_numpy(cm.make_instances(B, N, seed=9600 + N, random_contact_frac=1.0)).cuda()
     ids = cx.combo_ids(B, 3)
-    outs = []
-    for c in range(NC):
-        with mr.closing(shared(c, N, B)) as s:
-            outs.append(_condense_hook(s, recs, B, N, rows))
-    want = _rows_of(outs, ids)
-    with mr.closing(cost_handle(N, B, cx.table(B, 3))) as s:
-        got = _condense_hook(s, recs, B, N, rows)
+    got, want, outs = row_by_row(lambda s: _condense_hook(s, recs, B, N, rows), lambda c: shared(c, N, B),
+                                 lambda: cost_handle(N, B, cx.table(B, 3)), ids, NC)
     assert_same_bits(got, want, "condense")
     assert not np.array_equal(got[0][ids != 0], outs[0][0][ids != 0])
 
 
 def test_admm_row_by_row(cm, solver_mod):
     import torch
-    from test_gpu_admm import TIGHT
     N, B = 3, 16
     recs = torch.from_numpy(np.ascontiguousarray(cm.make_instances(B, N, seed=9699))).cuda()
     ids = cx.combo_ids(B, 0)
@@ -591,13 +506,8 @@ def test_admm_row_by_row(cm, solver_mod):
         torch.cuda.synchronize()
         return f.cpu().numpy(), status.cpu().numpy(), iters.cpu().numpy()
 
-    outs = []
-    for c in range(NC):
-        with mr.closing(shared(c, N, B)) as s:
-            outs.append(admm(s))
-    want = _rows_of(outs, ids)
-    with mr.closing(cost_handle(N, B, cx.table(B, 0))) as s:
-        got = admm(s)
+    got, want, outs = row_by_row(admm, lambda c: shared(c, N, B),
+                                 lambda: cost_handle(N, B, cx.table(B, 0)), ids, NC)
     assert_same_bits(got, want, "admm")
     assert (bits(got[0][ids != 0]) != bits(outs[0][0][ids != 0])).any(1).all()
 
@@ -628,7 +538,7 @@ def test_rollout_and_residual_do_not_read_the_cost(cm, solver_mod):
         torch.cuda.synchronize()
         return d_loco.cpu().numpy(), fext6.cpu().numpy(), est.cpu().numpy()
 
-    with mr.closing(solver_mod.BatchSolver(cm.make_params(N), max_batch=B)) as s:
+    with closing(solver_mod.BatchSolver(cm.make_params(N), max_batch=B)) as s:
         want = both(s)
         s.set_instance_costs(cx.table(B, 1))
         got = both(s)
@@ -644,9 +554,9 @@ def test_a_nan_velocity_refuses_that_instance_alone(cm, solver_mod):
     ids = cx.combo_ids(B, 2)
     want = rowwise(case, ids)
     hit = B // 2 + 1
-    recs[hit, importlib.import_module("quad-periodic-mpc_amd.records").REC_V + 1] = np.nan
-    with mr.closing(cost_handle(10, B, cx.table(B, 2))) as s:
-        f, st, it = run(s, recs)
+    recs[hit, records().REC_V + 1] = np.nan
+    with closing(cost_handle(10, B, cx.table(B, 2))) as s:
+        f, st, it = sentinel_solve(s, recs)
     assert st[hit] == BAD_INPUT and (bits(f[hit]) == 0).all()
     keep = np.arange(B) != hit
     for g, w in zip((f, st, it), want):
@@ -685,12 +595,12 @@ def test_closed_loop_tick_by_tick(cm, solver_mod):
 
     outs = []
     for c in range(NC):
-        with mr.closing(shared(c, N, B)) as s:
+        with closing(shared(c, N, B)) as s:
             outs.append(loop(s))
-    with mr.closing(cost_handle(N, B, cx.table(B, 0))) as s:
+    with closing(cost_handle(N, B, cx.table(B, 0))) as s:
         got = loop(s)
     for t in range(STEPS):
-        want = _rows_of([tuple(o[t]) for o in outs], ids)
+        want = rows_of([tuple(o[t]) for o in outs], ids)
         assert_same_bits(got[t], want, f"tick {t}")
         assert got[t][3].all() and (got[t][2] == 0).mean() > 0.9
     last = STEPS - 1

@@ -9,7 +9,7 @@ batches that reach every kernel family. The comparisons are of bits unless state
  2. under the mixed table, row i is row i of the shared handle of its combo solving the whole batch
     (every case, every rotation; with a due mask at N = 10 and N = 16);
  3. the mixed solve against the fp64 optimum of each row's own model and parameters
-    (instance_mix.cpu_data; tests/test_instance_params_ref.py is its CPU side), at the project's
+    (cost_mix.cpu_data with mix="model"; tests/test_instance_params_ref.py is its CPU side), at the project's
     gates: 1e-4 at N <= 10, 1e-5 from N = 11, status 0, swing legs exactly zero;
  4. one 16384-instance batch against four pieces of 4096 (the 60 / 64 split, the persistent builds);
  5. the life cycle: clear, set_params, set_model, batch > count, bad rows, an eliminating f_max;
@@ -22,89 +22,26 @@ import importlib
 import numpy as np
 import pytest
 
+import cost_mix as cx
 import instance_mix as im
 import model_ref as mr
 import param_sets as ps
-from test_gpu_due import ST_FILL, IT_FILL, bits, sentinel_forces
+import support
+from support import (FP64_TOL, IT_FILL, REF_TOL, ST_FILL, TIGHT, assert_same_bits, bits, closing, half_due,  # noqa: F401
+                     nan_where_not_due, package, row_by_row, sentinel_forces, sentinel_solve, solver,
+                     solver_mod)
 
 pytestmark = pytest.mark.gpu
 
-REF_TOL = 1e-4    # N <= 10: ours against the fp64 optimum
-FP64_TOL = 1e-5   # N >= 11 (refined)
-NC = len(im.COMBOS)
-
-
-@pytest.fixture(scope="module")
-def solver_mod():
-    mod = importlib.import_module("quad-periodic-mpc_amd.solver")
-    mod.load_library()
-    return mod
-
-
-def _smod():
-    return importlib.import_module("quad-periodic-mpc_amd.solver")
-
-
-def run(s, recs, due=None):
-    """One device solve into sentinel-filled buffers -> (forces, status, iters)."""
-    import torch
-    B, oc = recs.shape[0], s.out_cols
-    r = torch.from_numpy(np.array(recs, np.float32)).cuda()
-    f = torch.from_numpy(sentinel_forces(B, oc)).cuda()
-    st = torch.full((B,), ST_FILL, dtype=torch.uint8, device="cuda")
-    it = torch.full((B,), IT_FILL, dtype=torch.int32, device="cuda")
-    dd = None if due is None else torch.from_numpy(np.array(due, np.uint8)).cuda()
-    torch.cuda.synchronize()
-    s.solve(r, f, st, it, due=dd)
-    torch.cuda.synchronize()
-    return f.cpu().numpy(), st.cpu().numpy(), it.cpu().numpy()
-
-
-def assert_same_bits(got, want, msg=""):
-    for a, b in zip(got, want):
-        np.testing.assert_array_equal(bits(a), bits(b), err_msg=msg)
-
-
-def shared(k, N, B):
-    """A fresh shared handle of combo k."""
-    return _smod().BatchSolver(im.combo_params(k, N), max_batch=B, model=im.combo_model(k))
+NC = im.NC
+shared = functools.partial(support.shared_handle, im)   # (k, N, B): a fresh shared handle of combo k
+shared_solve = functools.partial(support.shared_solve, im)   # (k, case): its solve of the whole batch, cached
+rowwise = functools.partial(support.rowwise, im)   # (case, ids): row i of the shared handle of combo ids[i]
 
 
 def table_handle(N, B, tab):
     """A default handle (default model, mu 0.4, f_max 120) with the table set."""
-    return _smod().BatchSolver(importlib.import_module("quad-periodic-mpc_amd").make_params(N), max_batch=B,
-                               instance_params=tab)
-
-
-def half_due(B, seed=5):
-    due = np.zeros(B, np.uint8)
-    due[np.random.default_rng(seed).choice(B, B // 2, replace=False)] = 1
-    return due
-
-
-def nan_where_not_due(recs, due):
-    """The records with every word of the instances that are not due set to NaN."""
-    out = np.array(recs, np.float32)
-    out[due == 0] = np.nan
-    return out
-
-
-@functools.lru_cache(maxsize=None)
-def shared_solve(k, case):
-    """(forces, status, iters) of the case's whole batch on the shared handle of combo k; once per process."""
-    N = ps.CASES[case][0]
-    recs = ps.case_records("default", case)
-    with mr.closing(shared(k, N, len(recs))) as s:
-        out = run(s, recs)
-    for a in out:
-        a.setflags(write=False)
-    return out
-
-
-def rowwise(case, ids):
-    """Row i of the shared handle of combo ids[i]."""
-    outs = [shared_solve(k, case) for k in range(NC)]
-    return tuple(np.stack([outs[k][j][i] for i, k in enumerate(ids)]) for j in range(3))
+    return solver().BatchSolver(package().make_params(N), max_batch=B, instance_params=tab)
 
 
 # ---- 1: a uniform table is the shared handle ---------------------------------------------------------
@@ -116,17 +53,17 @@ def test_uniform_table_is_the_shared_handle(cm, solver_mod, case, masked):
     B = len(recs)
     due = half_due(B) if masked else None
     rin = nan_where_not_due(recs, due) if masked else recs
-    with mr.closing(shared(1, N, B)) as s:
-        want = run(s, rin, due)
+    with closing(shared(1, N, B)) as s:
+        want = sentinel_solve(s, rin, due)
         assert s.instance_count == 0
     m = np.ones(B, bool) if due is None else due != 0
     assert (want[1][m] == 0).mean() > 0.9 and (want[1][~m] == ST_FILL).all()
     np.testing.assert_array_equal(bits(want[0][~m]), bits(sentinel_forces(B, 12 * N)[~m]))
-    with mr.closing(table_handle(N, B, im.combo_rows(np.full(B, 1)))) as s:
+    with closing(table_handle(N, B, im.combo_rows(np.full(B, 1)))) as s:
         assert s.instance_count == B
-        assert_same_bits(run(s, rin, due), want, "uniform table of combo 1")
-    with mr.closing(solver_mod.BatchSolver(cm.make_params(N), max_batch=B)) as s:
-        assert not np.array_equal(bits(run(s, rin, due)[0])[m], bits(want[0])[m])   # combo 1 is not the default
+        assert_same_bits(sentinel_solve(s, rin, due), want, "uniform table of combo 1")
+    with closing(solver_mod.BatchSolver(cm.make_params(N), max_batch=B)) as s:
+        assert not np.array_equal(bits(sentinel_solve(s, rin, due)[0])[m], bits(want[0])[m])   # combo 1 is not the default
 
 
 # ---- 2: the mixed table, row by row -----------------------------------------------------------------
@@ -141,8 +78,8 @@ def test_mixed_table_row_by_row(cm, solver_mod, case, s_rot):
         counts = ps.family_counts(recs)
         assert min(counts) > 0, counts   # c1-60, c1-64, tail, w80, w96, w120
     want = rowwise(case, ids)
-    with mr.closing(table_handle(N, B, im.table(B, s_rot))) as s:
-        got = run(s, recs)
+    with closing(table_handle(N, B, im.table(B, s_rot))) as s:
+        got = sentinel_solve(s, recs)
     assert_same_bits(got, want, f"{case} rotation {s_rot}")
     assert (got[1] == 0).mean() > 0.9
     dflt = shared_solve(0, case)
@@ -160,8 +97,8 @@ def test_mixed_table_under_a_due_mask(cm, solver_mod, case, s_rot):
     due = half_due(B, seed=7 + s_rot)
     m = due != 0
     want = rowwise(case, ids)
-    with mr.closing(table_handle(N, B, im.table(B, s_rot))) as s:
-        got = run(s, nan_where_not_due(recs, due), due)
+    with closing(table_handle(N, B, im.table(B, s_rot))) as s:
+        got = sentinel_solve(s, nan_where_not_due(recs, due), due)
     for g, w in zip(got, want):
         np.testing.assert_array_equal(bits(g[m]), bits(w[m]))   # row i is row i of the table, mask or not
     np.testing.assert_array_equal(bits(got[0][~m]), bits(sentinel_forces(B, 12 * N)[~m]))
@@ -174,11 +111,11 @@ def test_mixed_table_against_the_fp64_optimum(cm, orc, solver_mod, case):
     """Measured on an MI355X when this test was written: see DESIGN.md §3.3."""
     if not orc.ref_available():
         pytest.skip("oracle/_ref not present")
-    d = im.cpu_data(case, 0)
+    d = cx.cpu_data(case, 0, mix="model")
     N, recs, ids, x64 = d["N"], d["recs"], d["ids"], d["x64"]
     assert (d["ri64"] == 0).all(), d["ri64"]
-    with mr.closing(table_handle(N, len(recs), im.table(len(recs), 0))) as s:
-        f, st, it = run(s, recs)
+    with closing(table_handle(N, len(recs), im.table(len(recs), 0))) as s:
+        f, st, it = sentinel_solve(s, recs)
     e64 = ps.rel_dist(f, x64)
     per = [float(e64[ids == k].max()) for k in range(NC)]
     print(f"[inst] {case}: {len(recs)} instances under the mix, ours within {e64.max():.1e} of the fp64 optimum "
@@ -200,10 +137,10 @@ def test_launch_forms_agree_under_the_mix(cm, solver_mod, N):
     prm = cm.make_params(N)
     recs = cm.make_instances(B, N, seed=8400 + N, random_contact_frac=1.0)
     tab = im.table(B, 1)
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=B, instance_params=tab)) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=B, instance_params=tab)) as s:
         f_all, st_all, it_all = s.solve_host(recs)
     parts = []
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=P)) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=P)) as s:
         for a in range(0, B, P):
             s.set_instance_params(tab[a:a + P])
             parts.append(s.solve_host(recs[a:a + P]))
@@ -211,7 +148,7 @@ def test_launch_forms_agree_under_the_mix(cm, solver_mod, N):
     diff = np.nonzero((bits(f_p) != bits(f_all)).any(1) | (st_p != st_all) | (it_p != it_all))[0]
     assert diff.size == 0, (diff.size, diff[:8])
     assert (st_all == 0).mean() > 0.99
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=P)) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=P)) as s:
         f_def = s.solve_host(recs[:P])[0]
     ids = im.combo_ids(P, 1)
     same = (bits(f_def) == bits(f_all[:P])).all(1)
@@ -228,35 +165,35 @@ def test_clear_and_survive(cm, solver_mod):
     tab = im.table(B, 2)
     want10 = rowwise("n10_families", im.combo_ids(B, 2))
     want16 = rowwise("n16_trot", im.combo_ids(len(recs16), 2))
-    with mr.closing(solver_mod.BatchSolver(p10, max_batch=B)) as s:
-        fresh = run(s, recs10)
+    with closing(solver_mod.BatchSolver(p10, max_batch=B)) as s:
+        fresh = sentinel_solve(s, recs10)
         s.set_instance_params(tab)
         assert s.instance_count == B
-        assert_same_bits(run(s, recs10), want10, "table set")
+        assert_same_bits(sentinel_solve(s, recs10), want10, "table set")
         s.set_params(p16)                                  # the table survives set_params ...
         assert s.instance_count == B
-        assert_same_bits(run(s, recs16), want16, "N = 16 under the same table")
+        assert_same_bits(sentinel_solve(s, recs16), want16, "N = 16 under the same table")
         s.set_params(p10)
-        assert_same_bits(run(s, recs10), want10, "back at N = 10")
+        assert_same_bits(sentinel_solve(s, recs10), want10, "back at N = 10")
         s.set_model(mr.model("x2"))                        # ... and set_model, which stays hidden
         assert s.model.mass == 24.0
-        assert_same_bits(run(s, recs10), want10, "set_model under a table")
+        assert_same_bits(sentinel_solve(s, recs10), want10, "set_model under a table")
         s.set_model(None)
         s.set_instance_params(None)                        # clear: a fresh handle's bits
         assert s.instance_count == 0
-        assert_same_bits(run(s, recs10), fresh, "cleared")
+        assert_same_bits(sentinel_solve(s, recs10), fresh, "cleared")
         s.set_model(mr.model("heavy"))
         s.set_params(im.combo_params(1, 10))
         s.set_instance_params(tab)
         s.set_instance_params(None)                        # what was set under the table shows again
-        assert_same_bits(run(s, recs10), shared_solve(1, "n10_families"), "shared values after a clear")
+        assert_same_bits(sentinel_solve(s, recs10), shared_solve(1, "n10_families"), "shared values after a clear")
 
 
 def test_batch_beyond_the_table_is_refused(cm, solver_mod):
     import torch
     recs = ps.case_records("default", "n3_padding")
     B = len(recs)
-    with mr.closing(solver_mod.BatchSolver(cm.make_params(3), max_batch=B)) as s:
+    with closing(solver_mod.BatchSolver(cm.make_params(3), max_batch=B)) as s:
         s.set_instance_params(im.table(B - 8, 0))
         assert s.instance_count == B - 8
         r = torch.from_numpy(np.array(recs)).cuda()
@@ -297,17 +234,17 @@ def test_bad_rows_are_rejected(cm, solver_mod):
                 [1e-39] + D + [0.4, 120.0], [12.0, 1e-310, 0.26, 0.242, 0.4, 120.0],
                 [12.0] + D + [0.0, 120.0], [12.0] + D + [-0.4, 120.0], [12.0] + D + [0.4, nan],
                 [12.0] + D + [nan, 120.0], [12.0] + D + [0.4, inf], [12.0] + D + [1e-50, 120.0]]
-    with mr.closing(solver_mod.BatchSolver(cm.make_params(3), max_batch=B)) as s:
-        fresh = run(s, recs)
+    with closing(solver_mod.BatchSolver(cm.make_params(3), max_batch=B)) as s:
+        fresh = sentinel_solve(s, recs)
         for row in bad_rows[:3]:                            # no table yet: none afterwards
             t = good.copy()
             t[B // 2] = row
             with pytest.raises(solver_mod.CmpcError, match=r"\(-2\)"):
                 s.set_instance_params(t)
             assert s.instance_count == 0
-        assert_same_bits(run(s, recs), fresh, "a rejected first table")
+        assert_same_bits(sentinel_solve(s, recs), fresh, "a rejected first table")
         s.set_instance_params(good)
-        want = run(s, recs)
+        want = sentinel_solve(s, recs)
         assert not np.array_equal(bits(want[0]), bits(fresh[0]))
         for row in bad_rows:
             t = im.table(B, 2)
@@ -315,7 +252,7 @@ def test_bad_rows_are_rejected(cm, solver_mod):
             with pytest.raises(solver_mod.CmpcError, match=r"\(-2\)"):
                 s.set_instance_params(t)
             assert s.instance_count == B
-        assert_same_bits(run(s, recs), want, "after rejected tables")
+        assert_same_bits(sentinel_solve(s, recs), want, "after rejected tables")
     with pytest.raises(solver_mod.CmpcError):
         bad = good.copy()
         bad[0, 0] = -1.0
@@ -333,8 +270,8 @@ def test_an_eliminating_f_max_is_that_instance_alone(cm, solver_mod):
     tab = im.table(B, 0)
     hit = [3, B // 2, B - 1]
     tab[hit, cm.INST_FMAX] = 0.005
-    with mr.closing(table_handle(10, B, tab)) as s:
-        f, st, it = run(s, recs)
+    with closing(table_handle(10, B, tab)) as s:
+        f, st, it = sentinel_solve(s, recs)
     keep = np.ones(B, bool)
     keep[hit] = False
     assert (f[hit] == 0.0).all() and (st[hit] == 0).all()
@@ -343,26 +280,14 @@ def test_an_eliminating_f_max_is_that_instance_alone(cm, solver_mod):
 
 
 # ---- 6: the other entry points, row by row against the shared handles --------------------------------
-def _rows_of(outs, ids):
-    """outs[k]: an array (or tuple of arrays) of combo k's shared handle -> row i from combo ids[i]."""
-    if isinstance(outs[0], tuple):
-        return tuple(_rows_of([o[j] for o in outs], ids) for j in range(len(outs[0])))
-    return np.stack([outs[k][i] for i, k in enumerate(ids)])
-
-
 @pytest.mark.parametrize("case,k", [("n10_families", 32), ("n20_standing", 4)])
 def test_evaluate_row_by_row(cm, solver_mod, case, k):
     N = ps.CASES[case][0]
     recs = ps.case_records("default", case)[:k]
     ids = im.combo_ids(k, 1)
     f = rowwise(case, im.combo_ids(len(ps.case_records("default", case)), 1))[0][:k]
-    outs = []
-    for c in range(NC):
-        with mr.closing(shared(c, N, k)) as s:
-            outs.append(s.evaluate_host(recs, f))
-    want = _rows_of(outs, ids)
-    with mr.closing(table_handle(N, k, im.table(k, 1))) as s:
-        got = s.evaluate_host(recs, f)
+    got, want, outs = row_by_row(lambda s: s.evaluate_host(recs, f), lambda c: shared(c, N, k),
+                                 lambda: table_handle(N, k, im.table(k, 1)), ids, NC)
     np.testing.assert_array_equal(bits(got[0]), bits(want[0]))                       # x_pred
     np.testing.assert_array_equal(got[1].view(np.uint64), want[1].view(np.uint64))   # all eight words
     assert not np.array_equal(got[1][ids != 0], outs[0][1][ids != 0])
@@ -385,13 +310,8 @@ def test_condense_row_by_row(cm, solver_mod, N, rows):
         torch.cuda.synchronize()
         return H.cpu().numpy(), g.cpu().numpy()
 
-    outs = []
-    for c in range(NC):
-        with mr.closing(shared(c, N, B)) as s:
-            outs.append(hook(s))
-    want = _rows_of(outs, ids)
-    with mr.closing(table_handle(N, B, im.table(B, 3))) as s:
-        got = hook(s)
+    got, want, outs = row_by_row(hook, lambda c: shared(c, N, B),
+                                 lambda: table_handle(N, B, im.table(B, 3)), ids, NC)
     assert_same_bits(got, want, "condense")
     assert not np.array_equal(got[0][ids != 0], outs[0][0][ids != 0])
 
@@ -418,13 +338,8 @@ def test_rollout_row_by_row(cm, solver_mod):
         torch.cuda.synchronize()
         return d_loco.cpu().numpy()
 
-    outs = []
-    for c in range(NC):
-        with mr.closing(shared(c, N, B)) as s:
-            outs.append(step(s))
-    want = _rows_of(outs, ids)
-    with mr.closing(table_handle(N, B, im.table(B, 2))) as s:
-        got = step(s)
+    got, want, outs = row_by_row(step, lambda c: shared(c, N, B),
+                                 lambda: table_handle(N, B, im.table(B, 2)), ids, NC)
     np.testing.assert_array_equal(bits(got), bits(want))
     np.testing.assert_array_equal(bits(got[due == 0]), bits(loco[due == 0]))
     m = (due != 0) & (ids != 0)
@@ -450,14 +365,10 @@ def test_residual_row_by_row(cm, solver_mod):
         torch.cuda.synchronize()
         return fext6.cpu().numpy()
 
-    outs = []
-    for c in range(NC):
-        with mr.closing(shared(c, N, B)) as s:
-            outs.append(resid(s, False))
-    want = _rows_of(outs, ids)
-    with mr.closing(table_handle(N, B, im.table(B, 1))) as s:
-        got = resid(s, False)
-        got_due = resid(s, True)
+    # (every handle runs both forms, the masked one behind the full one; the shared handles' masked output is not used)
+    got, want, outs = row_by_row(lambda s: (resid(s, False), resid(s, True)), lambda c: shared(c, N, B),
+                                 lambda: table_handle(N, B, im.table(B, 1)), ids, NC)
+    (got, got_due), want, outs = got, want[0], [o[0] for o in outs]
     np.testing.assert_array_equal(bits(got), bits(want))
     np.testing.assert_array_equal(bits(got_due[due != 0]), bits(want[due != 0]))
     assert np.isnan(got_due[due == 0]).all()
@@ -467,7 +378,6 @@ def test_residual_row_by_row(cm, solver_mod):
 
 def test_admm_row_by_row(cm, solver_mod):
     import torch
-    from test_gpu_admm import TIGHT
     N, B = 3, 16
     recs_np = cm.make_instances(B, N, seed=9599)
     recs = torch.from_numpy(np.ascontiguousarray(recs_np)).cuda()
@@ -485,12 +395,7 @@ def test_admm_row_by_row(cm, solver_mod):
         torch.cuda.synchronize()
         return f.cpu().numpy(), status.cpu().numpy(), iters.cpu().numpy()
 
-    outs = []
-    for c in range(NC):
-        with mr.closing(shared(c, N, B)) as s:
-            outs.append(admm(s))
-    want = _rows_of(outs, ids)
-    with mr.closing(table_handle(N, B, im.table(B, 0))) as s:
-        got = admm(s)
+    got, want, outs = row_by_row(admm, lambda c: shared(c, N, B),
+                                 lambda: table_handle(N, B, im.table(B, 0)), ids, NC)
     assert_same_bits(got, want, "admm")
     assert (bits(got[0][ids != 0]) != bits(outs[0][0][ids != 0])).any(1).all()

@@ -33,24 +33,15 @@ import evaluate_ref as er
 import model_ref as mr
 import param_sets as ps
 from conftest import PARITY_LEDGER, rel_force_err
-from test_gpu_due import ST_FILL, IT_FILL, bits, sentinel_forces
-from test_gpu_gradient_moments import _hook_records
-from test_gpu_parity import COND_BOUND, FP64_TOL
+from support import (COND_BOUND, FP64_TOL, REF_TOL, ST_FILL, TIGHT, abi_solve, assert_same_bits,  # noqa: F401
+                     assert_swing_zero, bits, closing, hook_records, sentinel_solve, solver, solver_mod)
 
 pytestmark = pytest.mark.gpu
 
-REF_TOL = 1e-4     # N <= 10: ours against the fp64 optimum
 VIOL_BAR = 2e-5    # test_gpu_evaluate.test_solve_then_evaluate: no row violated by more than this x max(1, |f|)
 SHORT_CASES = ["n10_families", "n16_trot", "n20_standing"]
 PARITY = ([(m, c) for m in ("heavy", "payload") for c in ps.CASES] +
           [(m, c) for m in ("x2", "massonly", "iperm") for c in SHORT_CASES])
-
-
-@pytest.fixture(scope="module")
-def solver_mod():
-    mod = importlib.import_module("quad-periodic-mpc_amd.solver")
-    mod.load_library()
-    return mod
 
 
 @pytest.fixture
@@ -61,24 +52,18 @@ def x64_ref(orc):
 
 
 def model_solve(solver_mod, prm, recs, mdl):
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=max(1, recs.shape[0]), model=mdl)) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=max(1, recs.shape[0]), model=mdl)) as s:
         return s.solve_host(recs)
 
 
 @functools.lru_cache(maxsize=None)
 def own_solve(model_name, case):
     """This solver's (forces, status, iters) of a (model set, case), solved once per process."""
-    solver_mod = importlib.import_module("quad-periodic-mpc_amd.solver")
     d = mr.cpu_data(model_name, case)
-    out = model_solve(solver_mod, d["prm"], d["recs"], mr.model(model_name))
+    out = model_solve(solver(), d["prm"], d["recs"], mr.model(model_name))
     for a in out:
         a.setflags(write=False)
     return out
-
-
-def assert_swing_zero(cm, recs, N, f):
-    swing = np.repeat(cm.unpack_gait(recs, N) == 0, 3, axis=1)
-    assert np.all(f[swing] == 0.0)
 
 
 # ---- parity against the fp64 optimum under the model ----------------------------------------------
@@ -112,7 +97,7 @@ def test_mini_is_feasible_and_reported(cm, x64_ref, solver_mod, case):
     d = mr.cpu_data("mini", case)
     prm, recs, x64 = d["prm"], d["recs"], d["x64"]
     f, st, it = own_solve("mini", case)
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=len(recs), model=mr.model("mini"))) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=len(recs), model=mr.model("mini"))) as s:
         _, c = s.evaluate_host(recs, f)
     e64 = ps.rel_dist(f, x64)
     r = c[:, er.GAP] / np.maximum(1.0, c[:, er.COST0])
@@ -129,26 +114,6 @@ def test_mini_is_feasible_and_reported(cm, x64_ref, solver_mod, case):
 
 
 # ---- the default model is the solver without a model, bit for bit ----------------------------------
-def _run(s, recs, due=None):
-    """One device solve into sentinel-filled buffers -> (forces, status, iters)."""
-    import torch
-    B, oc = recs.shape[0], s.out_cols
-    r = torch.from_numpy(np.array(recs, np.float32)).cuda()
-    f = torch.from_numpy(sentinel_forces(B, oc)).cuda()
-    st = torch.full((B,), ST_FILL, dtype=torch.uint8, device="cuda")
-    it = torch.full((B,), IT_FILL, dtype=torch.int32, device="cuda")
-    dd = None if due is None else torch.from_numpy(np.array(due, np.uint8)).cuda()
-    torch.cuda.synchronize()
-    s.solve(r, f, st, it, due=dd)
-    torch.cuda.synchronize()
-    return f.cpu().numpy(), st.cpu().numpy(), it.cpu().numpy()
-
-
-def assert_same_bits(got, want, msg=""):
-    for a, b in zip(got, want):
-        np.testing.assert_array_equal(bits(a), bits(b), err_msg=msg)
-
-
 @pytest.mark.parametrize("masked", [False, True], ids=["full", "due"])
 @pytest.mark.parametrize("case", ["n10_families", "n16_trot"])
 def test_default_model_is_bitwise(cm, solver_mod, case, masked):
@@ -161,26 +126,26 @@ def test_default_model_is_bitwise(cm, solver_mod, case, masked):
         due = np.zeros(B, np.uint8)
         due[np.random.default_rng(5).choice(B, B // 2, replace=False)] = 1
     heavy = mr.model("heavy")
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=B)) as fresh:
-        want = _run(fresh, recs, due)
+    with closing(solver_mod.BatchSolver(prm, max_batch=B)) as fresh:
+        want = sentinel_solve(fresh, recs, due)
         m0 = fresh.model
         assert (m0.mass, tuple(m0.inertia)) == mr.DEFAULT
     m = np.ones(B, bool) if due is None else due != 0
     assert (want[1][m] == 0).mean() > 0.9 and (want[1][~m] == ST_FILL).all()
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=B, model=cm.make_model())) as s:
-        assert_same_bits(_run(s, recs, due), want, "set_model(make_model())")
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=B)) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=B, model=cm.make_model())) as s:
+        assert_same_bits(sentinel_solve(s, recs, due), want, "set_model(make_model())")
+    with closing(solver_mod.BatchSolver(prm, max_batch=B)) as s:
         s.set_model(heavy)
-        got_heavy = _run(s, recs, due)
+        got_heavy = sentinel_solve(s, recs, due)
         assert not np.array_equal(bits(got_heavy[0])[m], bits(want[0])[m])
         s.set_model(cm.make_model())
-        assert_same_bits(_run(s, recs, due), want, "heavy and back")
+        assert_same_bits(sentinel_solve(s, recs, due), want, "heavy and back")
         s.set_model(heavy)
         s.set_model(None)
-        assert_same_bits(_run(s, recs, due), want, "heavy, then NULL")
+        assert_same_bits(sentinel_solve(s, recs, due), want, "heavy, then NULL")
         assert (s.model.mass, tuple(s.model.inertia)) == mr.DEFAULT
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=B, model=heavy)) as s:
-        assert_same_bits(_run(s, recs, due), got_heavy, "a handle created with the model")
+    with closing(solver_mod.BatchSolver(prm, max_batch=B, model=heavy)) as s:
+        assert_same_bits(sentinel_solve(s, recs, due), got_heavy, "a handle created with the model")
 
 
 @pytest.mark.parametrize("N", [16, 20])
@@ -196,7 +161,7 @@ def test_launch_forms_agree_under_model(cm, solver_mod, N):
     B = 16384
     recs = cm.make_instances(B, N, seed=8300 + N, random_contact_frac=1.0)
     f_all, st_all, it_all = model_solve(solver_mod, prm, recs, heavy)
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=4096, model=heavy)) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=4096, model=heavy)) as s:
         parts = [s.solve_host(recs[a:a + 4096]) for a in range(0, B, 4096)]
     f_p = np.concatenate([p[0] for p in parts])
     st_p = np.concatenate([p[1] for p in parts])
@@ -218,22 +183,22 @@ def test_model_persists_across_set_params(cm, solver_mod):
     p10, p10w, p16 = cm.make_params(10), ps.set_params("W1", 10), cm.make_params(16)
 
     def fresh(prm, mdl, recs):
-        with mr.closing(solver_mod.BatchSolver(prm, max_batch=len(recs), model=mdl)) as s:
-            return _run(s, recs)
+        with closing(solver_mod.BatchSolver(prm, max_batch=len(recs), model=mdl)) as s:
+            return sentinel_solve(s, recs)
 
-    with mr.closing(solver_mod.BatchSolver(p10, max_batch=len(recs10))) as s:
+    with closing(solver_mod.BatchSolver(p10, max_batch=len(recs10))) as s:
         s.set_model(heavy)
         s.set_params(p10w)                       # model first, then parameters
         assert s.model.mass == 20.0
-        assert_same_bits(_run(s, recs10), fresh(p10w, heavy, recs10), "set_model, set_params")
+        assert_same_bits(sentinel_solve(s, recs10), fresh(p10w, heavy, recs10), "set_model, set_params")
         s.set_params(p16)                        # another horizon: the refining wide classes
-        assert_same_bits(_run(s, recs16), fresh(p16, heavy, recs16), "set_params to N = 16")
+        assert_same_bits(sentinel_solve(s, recs16), fresh(p16, heavy, recs16), "set_params to N = 16")
         s.set_params(p10)
         s.set_model(payload)                     # parameters first, then model
-        assert_same_bits(_run(s, recs10), fresh(p10, payload, recs10), "set_params, set_model")
+        assert_same_bits(sentinel_solve(s, recs10), fresh(p10, payload, recs10), "set_params, set_model")
         s.set_params(p10w)
         s.set_model(None)
-        assert_same_bits(_run(s, recs10), fresh(p10w, None, recs10), "back to the default model")
+        assert_same_bits(sentinel_solve(s, recs10), fresh(p10w, None, recs10), "back to the default model")
     assert not np.array_equal(fresh(p10, heavy, recs10)[0], fresh(p10, payload, recs10)[0])
 
 
@@ -247,13 +212,13 @@ def test_bad_models_are_rejected(cm, solver_mod):
            cm.make_model(float("inf")), cm.make_model(12.0, (0.0, 0.26, 0.242)),
            # positive and finite, but 1.f / (float) mass and 1.0 / inertia overflow
            cm.make_model(1e-39), cm.make_model(12.0, (1e-310, 0.26, 0.242))]
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=len(recs), model=heavy)) as s:
-        want = _run(s, recs)
+    with closing(solver_mod.BatchSolver(prm, max_batch=len(recs), model=heavy)) as s:
+        want = sentinel_solve(s, recs)
         for b in bad:
             with pytest.raises(solver_mod.CmpcError, match=r"\(-2\)"):
                 s.set_model(b)
             assert (s.model.mass, tuple(s.model.inertia)) == mr.MODELS["heavy"]
-            assert_same_bits(_run(s, recs), want, "after a rejected model")
+            assert_same_bits(sentinel_solve(s, recs), want, "after a rejected model")
     for b in bad[:2]:
         with pytest.raises(solver_mod.CmpcError):
             solver_mod.set_model(b)
@@ -265,16 +230,16 @@ def test_bad_models_are_rejected(cm, solver_mod):
 @pytest.mark.parametrize("N", [1, 3, 10, 20])
 @pytest.mark.parametrize("model_name", ["heavy", "payload"])
 def test_hook_matches_fp64_condensation_under_model(cm, solver_mod, model_name, N):
-    """BatchSolver.condense against model_ref.fp64_condense on test_gpu_gradient_moments' eight hook
+    """BatchSolver.condense against model_ref.fp64_condense on support.hook_records' eight
     records, normwise, within COND_BOUND[N] (2e-6 below N = 10)."""
     import torch
     prm = cm.make_params(N)
     mdl = mr.model(model_name)
-    recs, _ = _hook_records(cm, N)
+    recs, _ = hook_records(cm, N)
     k = recs.shape[0]
     H = torch.zeros((k, 12 * N, 12 * N), dtype=torch.float32, device="cuda")
     g = torch.zeros((k, 12 * N), dtype=torch.float32, device="cuda")
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=k, model=mdl)) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=k, model=mdl)) as s:
         s.condense(torch.from_numpy(recs).cuda(), H, g)
         torch.cuda.synchronize()
     H = H.cpu().numpy(); g = g.cpu().numpy()
@@ -287,25 +252,6 @@ def test_hook_matches_fp64_condensation_under_model(cm, solver_mod, model_name, 
     print(f"[model] hook {model_name} N={N}: qg vs fp64 {worst_g:.2e}, qH vs fp64 {worst_h:.2e} (bound {bound:.0e})")
     assert worst_g <= bound, worst_g
     assert worst_h <= bound, worst_h
-
-
-def gap_bound(rec, prm, mdl, U, x64, dist):
-    """test_gpu_params.gap_bound with the model: an upper bound of the Frank-Wolfe gap of a feasible U
-    within ``dist`` (inf-norm, newtons) of the optimum, from the fp64 condensation (stance columns)."""
-    N = prm.horizon
-    ub, stance, mui = er._consts(rec, prm)
-    keep = np.repeat(stance, 3)
-    H, g = mr.fp64_condense(rec, prm, mdl)
-    U = np.asarray(U, np.float64)
-    grad = (H @ U + g).reshape(4 * N, 3)
-    mu = 1.0 / mui
-    y = np.zeros((4 * N, 3))
-    lift = stance & (ub * (grad[:, 2] - mu * np.abs(grad[:, 0]) - mu * np.abs(grad[:, 1])) < 0)
-    y[lift, 0] = -np.sign(grad[lift, 0]) * mu * ub[lift]
-    y[lift, 1] = -np.sign(grad[lift, 1]) * mu * ub[lift]
-    y[lift, 2] = ub[lift]
-    g_opt = (H @ x64 + g)[keep]
-    return dist * (np.abs(g_opt).sum() + np.abs((H @ (U - y.reshape(-1)))[keep]).sum())
 
 
 EVAL_K = 8   # leading instances of a case held against the test-side fp64 evaluation
@@ -323,9 +269,9 @@ def test_evaluate_own_solves_under_model(cm, x64_ref, solver_mod, model_name, ca
     prm, recs, x64 = d["prm"], d["recs"], d["x64"]
     mdl = mr.model(model_name)
     f, st, _ = own_solve(model_name, case)
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=len(recs), model=mdl)) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=len(recs), model=mdl)) as s:
         x, c = s.evaluate_host(recs, f)
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=len(recs))) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=len(recs))) as s:
         _, c_default = s.evaluate_host(recs, f)
     assert (st == 0).all()
     assert not np.array_equal(c[:, er.COST], c_default[:, er.COST])   # the model reaches the kernel
@@ -347,7 +293,8 @@ def test_evaluate_own_solves_under_model(cm, x64_ref, solver_mod, model_name, ca
     bounds = np.zeros(len(recs))
     for i in range(len(recs)):
         dist = tol * max(np.abs(x64[i]).max(), 1.0)
-        bounds[i] = gap_bound(recs[i], prm, mdl, f[i], x64[i], dist) + 1e-9 * max(1.0, c[i, er.COST0])
+        Hg = mr.fp64_condense(recs[i], prm, mdl)
+        bounds[i] = er.gap_bound(Hg, recs[i], prm, f[i], x64[i], dist) + 1e-9 * max(1.0, c[i, er.COST0])
         worst = max(worst, c[i, er.GAP] / bounds[i])
     print(f"[model] evaluate {model_name} {case}: worst ratio to the 1e-12 bars " +
           ", ".join(f"{n} {v.max():.2e}" for n, v in ratios.items()) +
@@ -381,7 +328,7 @@ def test_rollout_under_model(cm, solver_mod):
     d_loco = torch.from_numpy(loco.copy()).cuda()
     d_rec, d_u, d_xi, d_due = (torch.from_numpy(a).cuda() for a in (recs, u, xi, due))
     torch.cuda.synchronize()
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=B, model=mdl)) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=B, model=mdl)) as s:
         s.rollout(d_loco, d_rec, d_u, xi6=d_xi, due=d_due)
         torch.cuda.synchronize()
     got = d_loco.cpu().numpy()
@@ -406,7 +353,7 @@ def _residual_run(solver_mod, prm, recs, logs, mdl):
     est = torch.zeros((B, 816), dtype=torch.float32, device="cuda")
     fext6 = torch.full((B, 6), np.nan, dtype=torch.float32, device="cuda")
     torch.cuda.synchronize()
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=B)) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=B)) as s:
         if mdl != "never":
             s.set_model(mdl)
         s.estimate(est, d_rec, logs=d_log, sim_time=1.0, fext6=fext6)
@@ -456,7 +403,6 @@ def test_admm_follows_the_hook_under_model(cm, orc, solver_mod):
     the termination iteration agrees, 1e-3 otherwise). cmpc_batch_admm recomputes nothing from the
     model: it follows through H and g."""
     import torch
-    from test_gpu_admm import TIGHT
     N, B = 3, 16
     prm = cm.make_params(N)
     recs_np = cm.make_instances(B, N, seed=9399)
@@ -469,7 +415,7 @@ def test_admm_follows_the_hook_under_model(cm, orc, solver_mod):
     H0 = torch.empty_like(H)
     g0 = torch.empty_like(gv)
     torch.cuda.synchronize()
-    with mr.closing(solver_mod.BatchSolver(prm, max_batch=B)) as s:
+    with closing(solver_mod.BatchSolver(prm, max_batch=B)) as s:
         s.condense(recs, H0, g0)
         s.set_model(mr.model("heavy"))
         s.condense(recs, H, gv)
@@ -485,18 +431,6 @@ def test_admm_follows_the_hook_under_model(cm, orc, solver_mod):
 
 
 # ---- the reference surface ---------------------------------------------------------------------------
-def _abi_solve(solver_mod, cm, rec, prm):
-    N = prm.horizon
-    solver_mod.setup_problem(prm.dt, N, prm.mu, prm.f_max)
-    solver_mod.update_x_drag(float(rec[28]))
-    solver_mod.update_solver_settings(100, 1e-7, 1e-8, 1.5, 1e-5, 0)
-    gait = cm.unpack_gait(rec[None], N)[0].astype(np.int32)
-    solver_mod.update_problem_data_floats(rec[0:3], rec[3:6], rec[6:10], rec[10:13], rec[13:25],
-                                          rec[25], rec[26], rec[27], np.array(prm.weights),
-                                          rec[32:32 + 12 * N], prm.alpha, gait)
-    return np.array([solver_mod.get_solution(j) for j in range(12 * N)])
-
-
 @pytest.mark.parametrize("case", ["n10_families", "n16_trot"])
 def test_reference_surface_follows_the_model(cm, solver_mod, case):
     """In one process: set_model(heavy) -> update_problem_data_floats equals BatchSolver(model=heavy)
@@ -510,12 +444,12 @@ def test_reference_surface_follows_the_model(cm, solver_mod, case):
         for rec in recs:
             for mdl in (heavy, None, heavy):
                 solver_mod.set_model(mdl)
-                sol = _abi_solve(solver_mod, cm, rec, prm)
+                sol = abi_solve(solver_mod, cm, rec, prm)
                 f, st, _ = model_solve(solver_mod, prm, rec[None], mdl)
                 assert st[0] == 0
                 np.testing.assert_array_equal(sol, f[0].astype(np.float64))
                 _, cert = solver_mod.evaluate_last()
-                with mr.closing(solver_mod.BatchSolver(prm, max_batch=1, model=mdl)) as s:
+                with closing(solver_mod.BatchSolver(prm, max_batch=1, model=mdl)) as s:
                     _, c = s.evaluate_host(rec[None], f)
                 np.testing.assert_array_equal(cert, c[0])
             f_def, _, _ = model_solve(solver_mod, prm, rec[None], None)

@@ -37,7 +37,6 @@ cmpc_batch_set_params on a live handle (bitwise against fresh handles, with and 
 and the reference ABI switching weights within one process.
 """
 import functools
-import importlib
 
 import numpy as np
 import pytest
@@ -45,14 +44,13 @@ import pytest
 import evaluate_ref as er
 import param_sets as ps
 from conftest import PARITY_LEDGER, load_golden, rel_force_err
-from test_gpu_due import ST_FILL, IT_FILL, bits, sentinel_forces
-from test_gpu_gradient_moments import _hook_records
-from test_gpu_parity import COND_BOUND, FP64_TOL, assert_failed_reference, gpu_solve
+from support import (COND_BOUND, FP64_TOL, IT_FILL, REF_COND, REF_TOL, ST_FILL, abi_solve,  # noqa: F401
+                     assert_swing_zero, bits, gpu_solve, hook_records, package, sentinel_forces, sentinel_solve,
+                     solver, solver_mod)
+from test_gpu_parity import assert_failed_reference
 
 gpu = pytest.mark.gpu
 
-REF_TOL = 1e-4            # (a): ours against the reference pipeline and against the fp64 optimum
-REF_COND = 5e-5           # (a): the reference against the fp64 optimum, half the bar
 LOOSE_SETS = {"alpha1e-5": 1e-4, "dt0.04": 1e-4}   # (b): the worse-conditioned sets' bar
 
 
@@ -60,27 +58,14 @@ def gate_b(set_name):
     return LOOSE_SETS.get(set_name, FP64_TOL)
 
 
-@pytest.fixture(scope="module")
-def solver_mod():
-    mod = importlib.import_module("quad-periodic-mpc_amd.solver")
-    mod.load_library()
-    return mod
-
-
 @functools.lru_cache(maxsize=None)
 def own_solve(set_name, case):
     """This solver's (forces, status, iters) of a (set, case), solved once per process."""
-    solver_mod = importlib.import_module("quad-periodic-mpc_amd.solver")
     d = ps.cpu_data(set_name, case)
-    out = gpu_solve(solver_mod, d["prm"], d["recs"])
+    out = gpu_solve(solver(), d["prm"], d["recs"])
     for a in out:
         a.setflags(write=False)
     return out
-
-
-def assert_swing_zero(cm, recs, N, f):
-    swing = np.repeat(cm.unpack_gait(recs, N) == 0, 3, axis=1)
-    assert np.all(f[swing] == 0.0)
 
 
 @gpu
@@ -184,11 +169,11 @@ def test_optimum_sees_tampered_weights(orc, tamper, N):
 @pytest.mark.parametrize("set_name", ["W1", "dt0.013", "dt0.04", "all"])
 def test_hook_matches_fp64_condensation_under_set(cm, orc, solver_mod, set_name, N):
     """BatchSolver.condense against oracle.fp64_condense on the eight records of
-    test_gpu_gradient_moments._hook_records (history flag and f_est(3) on every other one), normwise,
+    support.hook_records (history flag and f_est(3) on every other one), normwise,
     within COND_BOUND[N] (2e-6 below N = 10)."""
     import torch
     prm = ps.set_params(set_name, N)
-    recs, _ = _hook_records(cm, N)
+    recs, _ = hook_records(cm, N)
     k = recs.shape[0]
     H = torch.zeros((k, 12 * N, 12 * N), dtype=torch.float32, device="cuda")
     g = torch.zeros((k, 12 * N), dtype=torch.float32, device="cuda")
@@ -209,28 +194,6 @@ def test_hook_matches_fp64_condensation_under_set(cm, orc, solver_mod, set_name,
           f"(bound {bound:.0e})")
     assert worst_g <= bound, worst_g
     assert worst_h <= bound, worst_h
-
-
-def gap_bound(orc, rec, prm, U, x64, dist):
-    """An upper bound of the Frank-Wolfe gap of a feasible U that is within ``dist`` (inf-norm, in
-    newtons) of the optimum U*. With d = U - U* and y the gap's maximiser at U,
-      gap(U) = grad(U).(U - y) = grad(U*).(U* - y) + grad(U*).d + d'H(U - y)
-             <= 0 + |d|_inf (|grad(U*)|_1 + |H (U - y)|_1),
-    the first term by U*'s optimality. Computed from the fp64 condensation (stance columns only)."""
-    N = prm.horizon
-    ub, stance, mui = er._consts(rec, prm)
-    keep = np.repeat(stance, 3)
-    H, g = orc.fp64_condense(rec, prm)
-    U = np.asarray(U, np.float64)
-    grad = (H @ U + g).reshape(4 * N, 3)
-    mu = 1.0 / mui
-    y = np.zeros((4 * N, 3))
-    lift = stance & (ub * (grad[:, 2] - mu * np.abs(grad[:, 0]) - mu * np.abs(grad[:, 1])) < 0)
-    y[lift, 0] = -np.sign(grad[lift, 0]) * mu * ub[lift]
-    y[lift, 1] = -np.sign(grad[lift, 1]) * mu * ub[lift]
-    y[lift, 2] = ub[lift]
-    g_opt = (H @ x64 + g)[keep]
-    return dist * (np.abs(g_opt).sum() + np.abs((H @ (U - y.reshape(-1)))[keep]).sum())
 
 
 @gpu
@@ -260,7 +223,8 @@ def test_evaluate_own_solves_under_set(cm, orc, solver_mod, set_name, case):
     worst = 0.0
     for i in range(len(recs)):
         dist = tol * max(np.abs(x64[i]).max(), 1.0)
-        bound = gap_bound(orc, recs[i], prm, f[i], x64[i], dist) + 1e-9 * max(1.0, c[i, er.COST0])
+        Hg = orc.fp64_condense(recs[i], prm)
+        bound = er.gap_bound(Hg, recs[i], prm, f[i], x64[i], dist) + 1e-9 * max(1.0, c[i, er.COST0])
         worst = max(worst, c[i, er.GAP] / bound)
         assert c[i, er.GAP] <= bound, (i, c[i, er.GAP], bound)
     r = c[:, er.GAP] / np.maximum(1.0, c[:, er.COST0])
@@ -278,28 +242,10 @@ LIVE_STEPS = [("params", ("default", 10)), ("params", ("all", 10)), ("params", (
 
 @functools.lru_cache(maxsize=None)
 def _live_records(set_name, N):
-    cm = importlib.import_module("quad-periodic-mpc_amd")
-    recs = cm.make_instances(LIVE_B, N, seed=9360 + N, dt=ps.SETS[set_name].get("dt", 0.026),
+    recs = package().make_instances(LIVE_B, N, seed=9360 + N, dt=ps.SETS[set_name].get("dt", 0.026),
                              random_contact_frac=1.0)
     recs.setflags(write=False)
     return recs
-
-
-def _run(s, recs, due=None):
-    """One device solve into sentinel-filled buffers sized for the full horizon -> (forces
-    [B, out_cols], status, iters, the force words past B x out_cols)."""
-    import torch
-    B, N, oc = recs.shape[0], s.horizon, s.out_cols
-    r = torch.from_numpy(np.array(recs, np.float32)).cuda()
-    f = torch.from_numpy(sentinel_forces(B, 12 * N)).cuda()
-    st = torch.full((B,), ST_FILL, dtype=torch.uint8, device="cuda")
-    it = torch.full((B,), IT_FILL, dtype=torch.int32, device="cuda")
-    dd = None if due is None else torch.from_numpy(np.array(due, np.uint8)).cuda()
-    torch.cuda.synchronize()
-    s.solve(r, f, st, it, due=dd)
-    torch.cuda.synchronize()
-    flat = f.cpu().numpy().reshape(-1)
-    return flat[:B * oc].reshape(B, oc).copy(), st.cpu().numpy(), it.cpu().numpy(), flat[B * oc:].copy()
 
 
 @gpu
@@ -336,15 +282,15 @@ def test_set_params_on_live_handle(cm, solver_mod, masked):
             if masked:
                 due = np.zeros(LIVE_B, np.uint8)
                 due[rng.choice(LIVE_B, LIVE_B // 2, replace=False)] = 1
-            got = _run(live, recs, due)
+            got = sentinel_solve(live, recs, due, full_horizon=True)
             fresh = solver_mod.BatchSolver(ps.set_params(state["set"], N), max_batch=LIVE_B)
             try:
                 if not state["refine"]:
                     fresh.set_refine(False)
                 if state["out_steps"]:
                     fresh.set_output_steps(state["out_steps"])
-                want = _run(fresh, recs, due)
-                full = _run(fresh, recs) if masked else want
+                want = sentinel_solve(fresh, recs, due, full_horizon=True)
+                full = sentinel_solve(fresh, recs, full_horizon=True) if masked else want
             finally:
                 fresh.close()
             oc = 12 * (state["out_steps"] if 0 < state["out_steps"] < N else N)
@@ -378,18 +324,6 @@ def test_set_params_on_live_handle(cm, solver_mod, masked):
     np.testing.assert_array_equal(last[2], first[2])
 
 
-def _abi_solve(solver_mod, cm, rec, prm):
-    N = prm.horizon
-    solver_mod.setup_problem(prm.dt, N, prm.mu, prm.f_max)
-    solver_mod.update_x_drag(float(rec[28]))
-    solver_mod.update_solver_settings(100, 1e-7, 1e-8, 1.5, 1e-5, 0)
-    gait = cm.unpack_gait(rec[None], N)[0].astype(np.int32)
-    solver_mod.update_problem_data_floats(rec[0:3], rec[3:6], rec[6:10], rec[10:13], rec[13:25],
-                                          rec[25], rec[26], rec[27], np.array(prm.weights),
-                                          rec[32:32 + 12 * N], prm.alpha, gait)
-    return np.array([solver_mod.get_solution(j) for j in range(12 * N)])
-
-
 @gpu
 def test_reference_abi_switches_parameters(cm, solver_mod):
     """test_gpu_parity.test_reference_call_protocol's loop with setup_problem(dt 0.02, mu 0.6,
@@ -403,10 +337,10 @@ def test_reference_abi_switches_parameters(cm, solver_mod):
     for i in range(4):
         rec = g["records"][i]
         for prm in (p_all, p_def):
-            sol = _abi_solve(solver_mod, cm, rec, prm)
+            sol = abi_solve(solver_mod, cm, rec, prm)
             f, st, _ = gpu_solve(solver_mod, prm, rec[None])
             assert st[0] == 0
             np.testing.assert_array_equal(sol, f[0].astype(np.float64))
             if prm is p_def:
                 assert rel_force_err(sol[None], g["q_ref"][i][None]).max() <= 1e-4
-        assert not np.array_equal(_abi_solve(solver_mod, cm, rec, p_all), sol)
+        assert not np.array_equal(abi_solve(solver_mod, cm, rec, p_all), sol)

@@ -29,6 +29,8 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN_SETS, PARITY_LEDGER, golden_params, load_golden, rel_force_err
+from status_cases import all_zero_force_records
+from support import COND_BOUND, FP64_TOL, abi_doubles, abi_floats, gpu_solve, solver_mod  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -39,7 +41,6 @@ def tol_for(N):
 
 ORDER_MIN_N = 11         # below this every instance is held to 1e-4 against the default-order
                          # reference (the first horizon at which the wide classes refine)
-FP64_TOL = 1e-5          # ours against the fp64 optimum on those instances (measured <= 4e-6)
 
 
 def assert_failed_reference(orc, recs, prm, f, st, st_ref, label=""):
@@ -101,21 +102,6 @@ def assert_parity(orc, recs, prm, f, q_ref, ok=None, label="", gait="trotting"):
     assert len(bad) == 0, (err.max(), int(np.argmax(err)))
 
 
-@pytest.fixture(scope="module")
-def solver_mod():
-    mod = importlib.import_module("quad-periodic-mpc_amd.solver")
-    mod.load_library()
-    return mod
-
-
-def gpu_solve(solver_mod, prm, recs):
-    s = solver_mod.BatchSolver(prm, max_batch=max(1, recs.shape[0]))
-    try:
-        return s.solve_host(recs)
-    finally:
-        s.close()
-
-
 @pytest.mark.parametrize("name", GOLDEN_SETS)
 def test_forces_match_qpoases_golden(cm, orc, solver_mod, name):
     g = load_golden(name)
@@ -131,15 +117,6 @@ def test_forces_match_qpoases_golden(cm, orc, solver_mod, name):
         gait = "standing" if ("standing" in name or "allstance" in name) else \
             ("walking" if "walking" in name else "trotting")
         assert_parity(orc, g["records"], prm, f, g["q_ref"], ok, label=f"golden {name}", gait=gait)
-
-
-# qH / qg of the structured condensation (cmpc_condense.hip) against the reference's dense fp32
-# GEMMs (the golden qH / qg, SolverMPC.cpp:806-814) and against the float64 condensation
-# (oracle.fp64_condense), normwise: max |difference| / max |qH| (qg likewise). The reference's own
-# fp32 qH is 2.2e-7 .. 5.5e-7 from the fp64 one on these fixtures (N = 10 .. 20), so the force
-# differences of up to ~1e-4 at N >= 16 (ORDER_MIN_N) come from the conditioning of the QP,
-# not from a drift of the condensed matrices.
-COND_BOUND = {10: 2e-6, 12: 2e-6, 16: 3e-6, 20: 4e-6}
 
 
 @pytest.mark.parametrize("name", ["n10_mixed", "n10_edge", "n12_allstance", "n16_standing", "n20_trot"])
@@ -277,24 +254,6 @@ def test_refine_switch_live(cm, orc, solver_mod, gait):
     PARITY_LEDGER.append(line)
 
 
-def _all_zero_force_records(cm, B, N=10, seed=5):
-    """n = 72 records (steps 0-5 all stance, 6-9 swing: the tail class) whose trajectory sinks
-    fast (z 0.3 m lower per step, v_z -6 m/s): the optimum is zero force on every foot, pinned by
-    three independent pyramid rows per stance foot-step, so the dual active set grows to 72
-    positions, past the tail class's 64 lanes."""
-    R = importlib.import_module("quad-periodic-mpc_amd.records")
-    recs = cm.make_instances(B, N, seed=seed, random_contact_frac=0.0, gait="standing")
-    g = np.zeros((B, 4 * N), np.uint8)
-    g[:, :24] = 1
-    recs[:, R.gait_offset(N):R.gait_offset(N) + N].view(np.uint8)[:, :] = g
-    traj = recs[:, R.REC_HDR:R.REC_HDR + 12 * N].reshape(B, N, 12)
-    for k in range(N):
-        traj[:, k, 5] = recs[:, R.REC_P + 2] - 0.3 * (k + 1)
-        traj[:, k, 11] = -6.0
-    recs[:, R.REC_HDR:R.REC_HDR + 12 * N] = traj.reshape(B, -1)
-    return recs
-
-
 def test_tail_class_hands_off_past_64_active(cm, orc, solver_mod):
     """The tail class's hand-off (cmpc_tail.hip): an instance whose active set outgrows the 64
     lanes is solved afresh by the 80-column class, in a batch (list 10, the one-workgroup launch
@@ -302,7 +261,7 @@ def test_tail_class_hands_off_past_64_active(cm, orc, solver_mod):
     The reference's qpOASES gives up on these (nWSR = 100); the fp64 optimum is zero force."""
     N, B = 10, 8
     prm = cm.make_params(N)
-    recs = _all_zero_force_records(cm, B, N)
+    recs = all_zero_force_records(cm, B, N)
     assert (3 * (cm.unpack_gait(recs, N) != 0).sum(1) == 72).all()
     f, st, it = gpu_solve(solver_mod, prm, recs)
     assert (st == 0).all(), st
@@ -425,23 +384,6 @@ def test_reference_call_protocol(cm, orc, solver_mod):
         assert rel_force_err(sol[None], g["q_ref"][i][None]).max() <= 1e-4
 
 
-def _abi_floats(solver_mod, cm, rec, N, prm, gait=None, traj=None):
-    gait = cm.unpack_gait(rec[None], N)[0].astype(np.int32) if gait is None else gait
-    traj = rec[32:32 + 12 * N] if traj is None else traj
-    solver_mod.update_problem_data_floats(rec[0:3], rec[3:6], rec[6:10], rec[10:13], rec[13:25],
-                                          rec[25], rec[26], rec[27], np.array(prm.weights),
-                                          traj, prm.alpha, gait)
-
-
-def _abi_doubles(solver_mod, cm, rec, N, prm, gait=None, traj=None):
-    gait = cm.unpack_gait(rec[None], N)[0].astype(np.int32) if gait is None else gait
-    traj = rec[32:32 + 12 * N] if traj is None else traj
-    solver_mod.update_problem_data(*(np.asarray(rec[a:b], np.float64) for a, b in
-                                     ((0, 3), (3, 6), (6, 10), (10, 13), (13, 25))),
-                                   float(rec[27]), np.array(prm.weights, np.float64),
-                                   np.asarray(traj, np.float64), float(prm.alpha), gait)
-
-
 @pytest.mark.parametrize("name", ["n10_mixed", "n16_trot"])
 def test_reference_call_protocol_double_variant(cm, orc, solver_mod, name):
     """update_problem_data (the double-precision entry point, convexMPC_interface.cpp:89-107:
@@ -455,9 +397,9 @@ def test_reference_call_protocol_double_variant(cm, orc, solver_mod, name):
         solver_mod.setup_problem(prm.dt, N, prm.mu, prm.f_max)
         solver_mod.update_x_drag(float(rec[28]))
         solver_mod.update_solver_settings(100, 1e-7, 1e-8, 1.5, 1e-5, 0)
-        _abi_doubles(solver_mod, cm, rec, N, prm)
+        abi_doubles(solver_mod, cm, rec, N, prm)
         sol_d = np.array([solver_mod.get_solution(j) for j in range(12 * N)])
-        _abi_floats(solver_mod, cm, rec, N, prm)
+        abi_floats(solver_mod, cm, rec, N, prm)
         sol_f = np.array([solver_mod.get_solution(j) for j in range(12 * N)])
         np.testing.assert_array_equal(sol_d, sol_f)
         if g["status"][i] == 0:
@@ -477,7 +419,7 @@ def test_reference_abi_rejects_horizon_beyond_max(cm, solver_mod, bad_N, capfd):
     solver_mod.setup_problem(prm.dt, 10, prm.mu, prm.f_max)
     solver_mod.update_x_drag(float(rec[28]))
     solver_mod.update_solver_settings(100, 1e-7, 1e-8, 1.5, 1e-5, 0)
-    _abi_floats(solver_mod, cm, rec, 10, prm)
+    abi_floats(solver_mod, cm, rec, 10, prm)
     prev = np.array([solver_mod.get_solution(j) for j in range(120)])
     assert rel_force_err(prev[None], g["q_ref"][5][None]).max() <= 1e-4
     capfd.readouterr()
@@ -485,8 +427,8 @@ def test_reference_abi_rejects_horizon_beyond_max(cm, solver_mod, bad_N, capfd):
     big_traj = np.tile(rec[32:44], M).astype(np.float32)
     big_gait = np.ones(4 * M, np.int32)
     solver_mod.setup_problem(prm.dt, bad_N, prm.mu, prm.f_max)
-    _abi_floats(solver_mod, cm, rec, M, prm, gait=big_gait, traj=big_traj)
-    _abi_doubles(solver_mod, cm, rec, M, prm, gait=big_gait, traj=big_traj)
+    abi_floats(solver_mod, cm, rec, M, prm, gait=big_gait, traj=big_traj)
+    abi_doubles(solver_mod, cm, rec, M, prm, gait=big_gait, traj=big_traj)
     err = capfd.readouterr().err
     assert "setup_problem: horizon" in err and err.count("previous solution kept") == 2, err
     after = np.array([solver_mod.get_solution(j) for j in range(max(12 * M, 120) + 12)])
@@ -497,7 +439,7 @@ def test_reference_abi_rejects_horizon_beyond_max(cm, solver_mod, bad_N, capfd):
     rec6 = g["records"][6]
     solver_mod.setup_problem(prm.dt, 10, prm.mu, prm.f_max)
     solver_mod.update_x_drag(float(rec6[28]))
-    _abi_floats(solver_mod, cm, rec6, 10, prm)
+    abi_floats(solver_mod, cm, rec6, 10, prm)
     sol6 = np.array([solver_mod.get_solution(j) for j in range(120)])
     assert rel_force_err(sol6[None], g["q_ref"][6][None]).max() <= 1e-4
 

@@ -20,41 +20,18 @@ by its constant cap of passes, the lists by their counts), and no address, lane 
 computed from a float (a NaN only ever loses a comparison: `sl < best`, `r > 0`, `zn > 1e-9 dn`,
 `d > 0` all take their "no" side)."""
 import ctypes
-import importlib
 
 import numpy as np
 import pytest
 
 import status_cases as sc
 from status_cases import BAD_INPUT, INFEASIBLE, MAX_ITER, NOT_PD, OK
-from test_gpu_due import Dev, assert_due_result, bits
-from test_gpu_parity import _abi_floats, _all_zero_force_records
 from conftest import golden_params, load_golden, rel_force_err
+from support import Dev, abi_floats, assert_due_result, assert_same, bits, records, solver_mod  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(10, 512), (16, 512), (20, 512), (10, 16384), (16, 16384), (20, 16384)]
-
-
-@pytest.fixture(scope="module")
-def solver_mod():
-    mod = importlib.import_module("quad-periodic-mpc_amd.solver")
-    mod.load_library()
-    return mod
-
-
-def _R():
-    return importlib.import_module("quad-periodic-mpc_amd.records")
-
-
-def assert_same(got, ref, rows=None, label=""):
-    """(forces, status, iters) of two solves bit for bit, over ``rows`` (a mask; None: all)."""
-    rows = slice(None) if rows is None else rows
-    for name, a, b in zip(("forces", "status", "iters"), got, ref):
-        a, b = bits(a)[rows], bits(b)[rows]
-        if not np.array_equal(a, b):
-            bad = np.nonzero((a != b).reshape(len(a), -1).any(axis=1))[0]
-            raise AssertionError(f"{label}: {name} differ in {bad.size} rows (first of the selection: {bad[:8]})")
 
 
 def poisoned(N, B):
@@ -135,7 +112,7 @@ def test_due_output_steps_and_instance_builds_on_poisoned_batch(cm, solver_mod, 
         due[sorted(cases)[::2]] = 0          # half of the poisoned rows are not due
         assert due[sorted(cases)].any() and not due[sorted(cases)].all()
         assert_due_result(d.run(bad, due), ref, due, d.cols)
-        d.s.set_instance_params(_R().make_instance_params(mass=np.full(B, 12.0)))
+        d.s.set_instance_params(records().make_instance_params(mass=np.full(B, 12.0)))
         assert d.s.instance_count == B
         assert_same(d.run(bad), ref, label="per-instance builds, default rows")
         assert_due_result(d.run(bad, due), ref, due, d.cols)
@@ -164,9 +141,9 @@ def test_tail_handoff_workgroup_isolation(cm, solver_mod):
     hand-off workgroup cannot see a failed instance ahead of a clean one: what this shows is that
     the tail class's failures leave the hand-off list and its six solves as they were."""
     N, B = 10, 8
-    R = _R()
+    R = records()
     prm = cm.make_params(N)
-    recs = _all_zero_force_records(cm, B, N)
+    recs = sc.all_zero_force_records(cm, B, N)
     assert (sc.reduced_sizes(recs, N) == 72).all()
     bad = np.array(recs)
     bad[1, R.REC_V + 2] = np.nan
@@ -319,7 +296,7 @@ def test_reference_abi_failed_solve(cm, solver_mod, capfd):
         solver_mod.setup_problem(prm.dt, N, prm.mu, prm.f_max)
         solver_mod.update_x_drag(float(rec[28]))
         solver_mod.update_solver_settings(100, 1e-7, 1e-8, 1.5, 1e-5, 0)
-        _abi_floats(solver_mod, cm, rec, N, prm)
+        abi_floats(solver_mod, cm, rec, N, prm)
         return np.array([solver_mod.get_solution(j) for j in range(12 * N)])
 
     ok_rows = [i for i in range(len(g["status"])) if g["status"][i] == 0][:3]
@@ -328,7 +305,7 @@ def test_reference_abi_failed_solve(cm, solver_mod, capfd):
     assert np.abs(first).max() > 1.0
     capfd.readouterr()
     bad = np.array(g["records"][ok_rows[1]])
-    bad[_R().REC_P + 1] = np.nan
+    bad[records().REC_P + 1] = np.nan
     sol = call(bad)
     ctypes.CDLL(None).fflush(None)   # the library prints through C stdio, block-buffered into a capture file
     out = capfd.readouterr().out

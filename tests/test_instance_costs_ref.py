@@ -22,16 +22,7 @@ import pytest
 
 import cost_mix as cx
 import param_sets as ps
-
-REF_TOL = 1e-4    # the N <= 10 gate
-FP64_TOL = 1e-5   # the N >= 11 gate
-REF_COND = 5e-5   # tests/test_gpu_params.py's condition on the inputs
-
-
-@pytest.fixture
-def needs_ref(orc):
-    if not orc.ref_available():
-        pytest.skip("oracle/_ref not present")
+from support import FP64_TOL, REF_COND, REF_TOL, needs_ref  # noqa: F401
 
 
 def test_make_instance_costs_layout(cm):

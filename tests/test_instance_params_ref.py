@@ -18,19 +18,10 @@ other tests of the float64 optimum are.
 import numpy as np
 import pytest
 
+import cost_mix as cx
 import instance_mix as im
-import model_ref as mr
 import param_sets as ps
-
-REF_TOL = 1e-4    # the N <= 10 gate
-FP64_TOL = 1e-5   # the N >= 11 gate
-REF_COND = 5e-5   # tests/test_gpu_params.py's condition on the inputs
-
-
-@pytest.fixture
-def needs_ref(orc):
-    if not orc.ref_available():
-        pytest.skip("oracle/_ref not present")
+from support import FP64_TOL, REF_COND, REF_TOL, needs_ref  # noqa: F401
 
 
 def test_make_instance_params_layout(cm):
@@ -58,11 +49,11 @@ def test_make_instance_params_layout(cm):
 
 @pytest.mark.parametrize("case", list(ps.CASES))
 def test_mix_is_solvable_and_rows_are_told_apart(needs_ref, case):
-    d = im.cpu_data(case, 0)
+    d = cx.cpu_data(case, 0, mix="model")
     N, recs, ids, x64 = d["N"], d["recs"], d["ids"], d["x64"]
     assert (d["ri64"] == 0).all(), d["ri64"]
     # the neighbour's combo
-    xn, rin = im.fp64_rows(recs, N, (ids + 1) % len(im.COMBOS))
+    xn, rin = cx.fp64_rows(recs, N, model_ids=(ids + 1) % len(im.COMBOS))
     assert (rin == 0).all(), rin
     move = ps.rel_dist(xn, x64)
     bar = 10 * (REF_TOL if N <= 10 else FP64_TOL)
@@ -73,8 +64,8 @@ def test_mix_is_solvable_and_rows_are_told_apart(needs_ref, case):
 
 @pytest.mark.parametrize("case", ["n10_families", "n3_padding"])
 def test_mix_fp32_condensation_condition(needs_ref, case):
-    d = im.cpu_data(case, 0)
-    x32, ri = im.fp64_rows(d["recs"], d["N"], d["ids"], dtype=np.float32)
+    d = cx.cpu_data(case, 0, mix="model")
+    x32, ri = cx.fp64_rows(d["recs"], d["N"], model_ids=d["ids"], dtype=np.float32)
     assert (ri == 0).all(), ri
     dist = ps.rel_dist(x32, d["x64"])
     per = [float(dist[d["ids"] == k].max()) for k in range(len(im.COMBOS))]

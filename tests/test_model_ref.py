@@ -25,25 +25,18 @@ import pytest
 
 import model_ref as mr
 import param_sets as ps
+from support import FP64_TOL, REF_COND, REF_TOL, needs_ref, package  # noqa: F401
 
-REF_TOL = 1e-4    # the N <= 10 gate (tests/test_gpu_params.py)
-FP64_TOL = 1e-5   # the N >= 11 gate (tests/test_gpu_parity.py)
-REF_COND = 5e-5   # tests/test_gpu_params.py's condition on the inputs
+pytestmark = pytest.mark.usefixtures("needs_ref")
 
 # case -> leading instances used
 DEFAULT_INPUTS = {"n10_families": 32, "n16_trot": 6, "n20_standing": 2}
 
 
-@pytest.fixture(autouse=True)
-def _needs_ref(orc):
-    if not orc.ref_available():
-        pytest.skip("oracle/_ref not present")
-
-
 @functools.lru_cache(maxsize=None)
 def _x64(model_key, case, k):
     """fp64 optimum of the case's first k records under a model given as (mass, inertia) or a name."""
-    cm = mr._cm()
+    cm = package()
     mdl = mr.model(model_key) if isinstance(model_key, str) else cm.make_model(*model_key)
     N = ps.CASES[case][0]
     x, ri = mr.fp64_batch(ps.case_records("default", case)[:k], ps.set_params("default", N), mdl)

@@ -6,7 +6,6 @@ test checks the sharding and the collectives: each rank gets exactly its contigu
 the gathered rows come back in instance order for uneven block sizes too."""
 import importlib
 import os
-import socket
 import sys
 
 import numpy as np
@@ -15,14 +14,7 @@ import torch
 import torch.multiprocessing as mp
 
 from conftest import ROOT
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
+from support import free_port
 
 
 def _fake_solve(records, N):
@@ -64,7 +56,7 @@ def _worker(rank, world, port, batch, N, q):
 def test_scatter_solve_gather_gloo(world, batch):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_worker, args=(r, world, port, batch, 10, q)) for r in range(world)]
     for p in procs:
         p.start()
@@ -160,7 +152,7 @@ def test_root_pipeline_pairwise_op_order(world, chunks):
     sides (world 2 and 3, 3 and 4 pieces), and the gathered forces must be complete."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     batch = 97
     procs = [ctx.Process(target=_pipe_worker, args=(r, world, port, batch, 10, chunks, q))
              for r in range(world)]
@@ -186,7 +178,7 @@ def test_root_pipeline_compact_records(world, chunks):
     the full records."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    port = _free_port()
+    port = free_port()
     procs = [ctx.Process(target=_pipe_worker, args=(r, world, port, 101, 10, chunks, q, "compact"))
              for r in range(world)]
     for p in procs:
