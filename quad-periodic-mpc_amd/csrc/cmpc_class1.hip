@@ -141,11 +141,10 @@ struct SharedC1 {
       float cs[2 * NL];    // Givens (c, s) per column pair
     } gi;
   } u;
-  float sub[C1_MAXFS];     // ub of each stance foot-step (gait * f_max)
+  float sub[C1_MAXFS];     // ub of each stance foot-step (gait * f_max): read once, into lane 3s+2
   int sfs[C1_MAXFS];       // stance foot-step ids, in order
   int blkbase[MAXN + 2];   // first reduced variable of each horizon step
   unsigned char varblk[NL], varcol[NL];
-  unsigned char cmask[NL];  // active flags of stance foot-step s's 6 constraints (bit t of byte s)
 };
 
 __device__ __forceinline__ void lsync() {
@@ -360,7 +359,6 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       const unsigned long long hi = (b1 <= 0) ? 0ull : (msk1 & ((1ull << b1) - 1ull));
       sh.blkbase[v] = 3 * (__popcll(lo) + __popcll(hi));
     }
-    for (int t = v; t < nfs; t += 64) sh.cmask[t] = 0;
   }
   Model md;
   if constexpr (INST) make_model<kModelFromInst>(srec, P.dt, P.mdl, md, ie);
@@ -746,7 +744,18 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
   float up = 0.f;
   bool rinv_ok = true;  // R^-1 kept beside R (wave-uniform)
   lsync();
+  // The selection's trip state sits in lane 3 s + 2, the lane of foot-step s's fz, which scores the
+  // foot-step: its upper bound and the active flags of its six constraints (bit t). Every other lane
+  // keeps all six flags set and so never offers a constraint.
+  float sub_reg = 0.f;
+  unsigned fm_reg = 0x3fu;
+  if (v < n && v % 3 == 2) {
+    sub_reg = sh.sub[v / 3];
+    fm_reg = 0u;
+  }
   if (status == CMPC_OK) {
+    // max |x| for the selection's tolerance, taken where x changes: off the selection's chain
+    float xmax = wave_max(fabsf(xv));
     for (;;) {
       pin(slot);
       const int v = tid_opq();  // re-materialised: keeps per-lane addresses out of the preheader
@@ -754,29 +763,29 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       t_sub = clock64();
 #endif
       if (p < 0) {
-        // foot-step v's forces from lanes 3v .. 3v+2 by ds_bpermute (no LDS store + reload)
-        const float fx = __shfl(xv, 3 * v), fy = __shfl(xv, 3 * v + 1), fz = __shfl(xv, 3 * v + 2);
+        // foot-step s is scored in lane 3 s + 2, which holds fz: fy and fx come down from lanes
+        // 3 s + 1 and 3 s by two wave shifts (DPP: no ds_bpermute, no LDS read on this chain)
+        const float fz = xv, fy = lane_prev(0.f, xv), fx = lane_prev(0.f, fy);
         float best = 0.f;
         int bid = 0x7fffffff;
-        if (v < nfs) {
-          const unsigned fm = sh.cmask[v];
+        {
           float sl[6];
           sl[0] = (mui * fx + fz) * fnorm;
           sl[1] = (-mui * fx + fz) * fnorm;
           sl[2] = (mui * fy + fz) * fnorm;
           sl[3] = (-mui * fy + fz) * fnorm;
           sl[4] = fz;
-          sl[5] = sh.sub[v] - fz;
+          sl[5] = sub_reg - fz;
+          // constraint 6 s + t = 2 (v - 2) + t in lane v = 3 s + 2
 #pragma unroll
           for (int t = 0; t < 6; t++)
-            if (!((fm >> t) & 1u) && sl[t] < best) { best = sl[t]; bid = 6 * v + t; }
+            if (!((fm_reg >> t) & 1u) && sl[t] < best) { best = sl[t]; bid = 2 * v - 4 + t; }
         }
-        const float xmax = wave_max(fabsf(xv));
         wave_argmin(best, bid);
         const float tol = 1e-5f * fmaxf(1.f, xmax);
         if (bid == 0x7fffffff || best >= -tol) break;
         p = __builtin_amdgcn_readfirstlane(bid);
-        cp = decode_cons(p, mui, sh.sub[p / 6]);
+        cp = decode_cons(p, mui, rl(sub_reg, 3 * (p / 6) + 2));
         up = 0.f;
       }
       C1_SUB(0);
@@ -870,6 +879,7 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
       if (v < q) u_reg = fmaf(-t, r_reg, u_reg);
       up += t;
       if (!zero_step) xv = fmaf(t, zv, xv);
+      xmax = wave_max(fabsf(xv));  // for the next selection: its DPP steps run under the R update's stores
       C1_SUB(2);
       const bool add = !zero_step && t2 <= t1;
       const bool add_u = __builtin_amdgcn_readfirstlane((int)add) != 0;
@@ -902,14 +912,14 @@ __device__ __forceinline__ void solve_c1(const float* __restrict__ rec, const KP
             rinv_ok = false;
           }
         }
-        if (v == 0) sh.cmask[p / 6] |= (unsigned char)(1u << (p % 6));
+        if (v == cp.iz) fm_reg |= 1u << (p % 6);  // (lane 3 (p / 6) + 2 owns the foot-step's flags)
       } else {
         // ---- drop active constraint kk: shift positions kk+1..q-1 down, remove column kk of
         // R and re-triangularise rows kk..q-1 (lane c rebuilds column c of R in place: every
         // read of an old entry precedes, in this wavefront's LDS order, the write reusing it)
         const int k = __builtin_amdgcn_readfirstlane(kk);
         const int ak = rli(act_reg, k);
-        if (v == 0) sh.cmask[ak / 6] &= (unsigned char)~(1u << (ak % 6));
+        if (v == 3 * (ak / 6) + 2) fm_reg &= ~(1u << (ak % 6));
         const int a_nx = lane_next_i(act_reg, act_reg);
         const float u_nx = lane_next(u_reg, u_reg);
         if (v >= k && v < q - 1) { act_reg = a_nx; u_reg = u_nx; }
