@@ -284,9 +284,10 @@ CMPC_EXTERNC int cmpc_batch_get_model(const cmpc_batch* h, cmpc_model* out);
  * handle keeps its previous table, or none. d_inst == NULL clears the table: the handle is then bit
  * for bit the handle it was before (shared model, mu and f_max).
  * While a table is set, instance i uses row i in place of the handle's model, mu and f_max in
- * cmpc_batch_solve, _solve_due, _solve_host, _condense, _condense_rows, _evaluate(_host), _rollout,
- * _estimate(_due) (the residual, when d_logs is given) and _admm (fmat and U_b); a row whose
- * |gait x f_max| < 0.01 eliminates every foot-step of that instance alone. Each of these calls with
+ * cmpc_batch_solve, _solve_due, _solve_host, _condense, _condense_rows, _evaluate(_host),
+ * _sensitivity(_host), _rollout, _estimate(_due) (the residual, when d_logs is given) and _admm
+ * (fmat and U_b); a row whose |gait x f_max| < 0.01 eliminates every foot-step of that instance
+ * alone. Each of these calls with
  * batch > count returns its bad-arguments error and writes nothing. cmpc_batch_get_model still
  * returns the handle's shared model; cmpc_batch_set_model and _set_params still work and the table
  * survives both: their model, mu and f_max become visible again when the table is cleared. The
@@ -318,10 +319,10 @@ CMPC_EXTERNC int cmpc_batch_instance_count(const cmpc_batch* h);   /* 0: none se
  * any bad row the call returns -2 and the handle keeps its previous table, or none. d_cost == NULL
  * clears the table: the handle is then bit for bit the handle it was before (shared weights, alpha).
  * While a table is set, instance i uses row i in place of the handle's weights and alpha in
- * cmpc_batch_solve, _solve_due, _solve_host, _condense, _condense_rows and _evaluate(_host);
- * _admm follows through the H and g it is given; _rollout, _estimate(_due), _assemble and _expand
- * read neither value. Each call that takes a batch returns its bad-arguments error and writes
- * nothing when batch > count.
+ * cmpc_batch_solve, _solve_due, _solve_host, _condense, _condense_rows, _evaluate(_host) and
+ * _sensitivity(_host); _admm follows through the H and g it is given; _rollout, _estimate(_due),
+ * _assemble and _expand read neither value. Each call that takes a batch returns its
+ * bad-arguments error and writes nothing when batch > count.
  * The cost table and the parameter table are independent: either, both or neither may be set, in
  * any order, and each is cleared on its own; with both set, batch must not exceed either count.
  * Both survive cmpc_batch_set_params and cmpc_batch_set_model; of the shared values a table does
@@ -417,6 +418,64 @@ CMPC_EXTERNC int cmpc_batch_evaluate_host(cmpc_batch* h, const float* records, c
  * Runs on request only, so the reference protocol's latency is untouched. Returns a negative
  * error before the first solve. New API. */
 CMPC_EXTERNC int cmpc_evaluate_last(float* x_pred, double* cert);
+/* Gradients of a loss L through the solve, by an fp64 Riccati adjoint: given forces U [batch * 12N]
+ * (any source, as for cmpc_batch_evaluate) and the upstream gradient V = dL/dU [batch * 12N], how L
+ * moves with the weights, alpha, the initial state, the reference trajectory and f_est(3). The QP,
+ * x_0, 1/mu, ub and the stance test are cmpc_batch_evaluate's, all in fp64. New API.
+ *   face:   a row of a stance foot-step is active when its normalised slack (the six expressions of
+ *           CMPC_CERT_VIOL, not negated) is <= act_tol newtons. The foot-step's free subspace Z_s is
+ *           the null space of its active rows' normals: interior (dimension 3), one friction side
+ *           (2), an x side and a y side (1), the cap fz = ub (2), cap and one side (1), cap and two
+ *           sides (0). A foot-step with fz at 0, or on both sides of one axis, is at the apex: all of
+ *           it is pinned (0). Swing foot-steps are pinned. Z = diag(Z_s), m = sum of the dimensions.
+ *   w     = -Z (Z'HZ)^-1 Z'V,  H = 2 (B_qp' S B_qp + alpha I): dL/dg of the minimiser over the face
+ *   dx    : the rollout of w from a zero state, dx_k+1 = Adt dx_k + Bdt w_k; x_k(U) as evaluate's
+ *   dL/dxd_k[j] = -2 W_j dx_k[j]                       (word j of traj row k)
+ *   dL/dx_0     = the first 12 components of lambda_0,  lambda <- Adt' lambda + 2 W dx_k backwards
+ *   dL/dW_j     = 2 sum_k dx_k[j] (x_k(U) - xd_k)[j]    (through H and g together)
+ *   dL/dalpha   = 2 w.U
+ *   dL/df_est(3) = sum_k lambda_k+1' Qdt e_3 when flag bit 0 is set, otherwise 0
+ * w solves an LQ problem over the 12 dynamic states with at most 12 inputs per step, by a Riccati
+ * recursion: O(N 12^3) operations at any horizon, no H formed.
+ * Out of scope: the rpy part of dL/dx_0 is the partial derivative at a fixed rotation matrix (the
+ * quaternion also forms R); nothing is returned for the derivative through R, the foot offsets r,
+ * x_drag, mass, inertia, mu, f_max or dt.
+ * Validity: the quantity is defined for any U: it is the derivative of the minimiser over the face
+ * U lies on. It equals the derivative of the solve when U is the optimum and no active row has a
+ * zero multiplier. At a weakly active row the solution map is only directionally differentiable;
+ * what is returned there is the derivative of one side, and this is not detected (CMPC_SENS_SLACK
+ * tells how near an inactive row is, nothing tells how near a multiplier is to 0). An instance whose
+ * forces are all zero (a failed status) has m = 0 and zero gradients. Non-finite forces, V or
+ * trajectory words give NaN in every word of d_sens but CMPC_SENS_FREE (d_dtraj and d_dg hold NaN
+ * only where the arithmetic carries it: they do not depend on the trajectory, for one); other
+ * non-finite record words give NaN in the words they reach.
+ * Outputs: d_sens [batch * CMPC_SENS_WORDS] fp64; d_dtraj [batch * 12N] fp64 = dL/dxd, step-major in
+ * the order of the traj rows, may be NULL; d_dg [batch * 12N] fp64 = w, may be NULL.
+ * Honours the handle's model and both per-instance tables as cmpc_batch_evaluate does. Asynchronous
+ * on the handle's stream; neither allocates nor synchronises. Returns 0 or a negative error: those
+ * of cmpc_batch_evaluate (bad batch, a NULL input, a NULL d_sens, a handle that keeps fewer than N
+ * output steps), and -2 for an act_tol that is negative or not finite. */
+#define CMPC_SENS_X0       0   /* 12: dL/dx_0 in the order of the traj rows (rpy, p, w, v)      */
+#define CMPC_SENS_WEIGHTS  12  /* 12: dL/dweights                                               */
+#define CMPC_SENS_ALPHA    24
+#define CMPC_SENS_FEST3    25
+#define CMPC_SENS_FREE     26  /* m, the face's dimension, as a double                          */
+#define CMPC_SENS_SLACK    27  /* smallest normalised slack of an inactive row of a stance      */
+                               /* foot-step (+inf when there is none): how near the face is to   */
+                               /* changing                                                       */
+#define CMPC_SENS_WORDS    32  /* 28..31 written as 0 */
+CMPC_EXTERNC int cmpc_batch_sensitivity(cmpc_batch* h, const float* d_records, const float* d_forces,
+                                        const float* d_grad_forces, int batch, double act_tol,
+                                        double* d_sens, double* d_dtraj, double* d_dg);
+/* Same, host buffers in and out (H2D + kernel + D2H on the handle's stream, synchronous). */
+CMPC_EXTERNC int cmpc_batch_sensitivity_host(cmpc_batch* h, const float* records, const float* forces,
+                                             const float* grad_forces, int batch, double act_tol,
+                                             double* sens, double* dtraj, double* dg);
+/* Single-instance surface: cmpc_batch_sensitivity of the record, the solution and the model of the
+ * last update_problem_data* call (grad_forces [12N]; sens [CMPC_SENS_WORDS]; dtraj, dg [12N] or
+ * NULL). Runs on request only. Returns a negative error before the first solve. New API. */
+CMPC_EXTERNC int cmpc_sensitivity_last(const float* grad_forces, double act_tol, double* sens,
+                                       double* dtraj, double* dg);
 /* Single-instance surface: the robot model from the next update_problem_data* call on, as
  * update_solver_settings sets its settings (m == NULL: the default; -2 and no change for a
  * non-finite or non-positive field). cmpc_evaluate_last evaluates under the model of the solve it

@@ -94,6 +94,9 @@ struct __attribute__((visibility("hidden"))) cmpc_batch {
   // outputs of cmpc_batch_evaluate_host (allocated on its first call, sized max_batch)
   DevBuf<float> d_xpred;
   DevBuf<double> d_cert;
+  // input and outputs of cmpc_batch_sensitivity_host (likewise)
+  DevBuf<float> d_gradf;
+  DevBuf<double> d_sens, d_dtraj, d_dg;
   // side streams + fork/join events for the wider size classes (cmpc_launch.hip)
   cmpc::LaunchCtx ctx;
   PinBuf<int> h_hint;            // ctx.h_hint: freed after the own stream is idle (cmpc_batch_destroy)
@@ -673,6 +676,10 @@ static void free_staging(cmpc_batch* h) {
   h->h_pin.reset();
   h->d_xpred.reset();
   h->d_cert.reset();
+  h->d_gradf.reset();
+  h->d_sens.reset();
+  h->d_dtraj.reset();
+  h->d_dg.reset();
   h->staged = false;
 }
 
@@ -847,6 +854,65 @@ extern "C" int cmpc_batch_evaluate_host(cmpc_batch* h, const float* records, con
     if (int r = stream_d2h(h, xpred, h->d_xpred.get(), sizeof(float) * 12 * N * batch)) return r;
   if (cert)
     if (int r = stream_d2h(h, cert, h->d_cert.get(), sizeof(double) * CMPC_CERT_WORDS * batch)) return r;
+  return stream_sync(h);
+}
+
+// what both sensitivity entry points ask of their arguments: evaluate's checks, and act_tol
+static int sensitivity_check(const char* who, const cmpc_batch* h, int batch, const void* records,
+                             const void* forces, const void* gradf, double act_tol, const void* sens) {
+  if (!sens) {
+    g_last_error = std::string(who) + ": sens is NULL";
+    return -1;
+  }
+  if (int r = evaluate_check(who, h, batch, records, forces, sens, sens, ", its forces are not a full solution"))
+    return r;
+  if (batch && !gradf) return bad_arguments(who);
+  if (!std::isfinite(act_tol) || act_tol < 0.0) {
+    g_last_error = std::string(who) + ": act_tol is negative or not finite";
+    return -2;
+  }
+  return 0;
+}
+
+extern "C" int cmpc_batch_sensitivity(cmpc_batch* h, const float* d_records, const float* d_forces,
+                                      const float* d_grad_forces, int batch, double act_tol, double* d_sens,
+                                      double* d_dtraj, double* d_dg) {
+  if (int r = sensitivity_check("cmpc_batch_sensitivity", h, batch, d_records, d_forces, d_grad_forces, act_tol,
+                                d_sens))
+    return r;
+  return checked("launch_sensitivity",
+                 cmpc::launch_sensitivity(d_records, d_forces, d_grad_forces, batch, h->kp, (double)h->prm.alpha,
+                                          h->model.inertia, act_tol, d_sens, d_dtraj, d_dg, h->stream,
+                                          h->d_inst_rows.get()));
+}
+
+extern "C" int cmpc_batch_sensitivity_host(cmpc_batch* h, const float* records, const float* forces,
+                                           const float* grad_forces, int batch, double act_tol, double* sens,
+                                           double* dtraj, double* dg) {
+  if (int r = sensitivity_check("cmpc_batch_sensitivity_host", h, batch, records, forces, grad_forces, act_tol, sens))
+    return r;
+  if (batch == 0) return 0;
+  if (int r = ensure_staging(h)) return r;
+  hipError_t e;
+  const size_t B = (size_t)h->max_batch;
+  if (!h->d_gradf && (e = h->d_gradf.alloc(Stage::kForcesMax * B)) != hipSuccess) return fail("hipMalloc(grad_forces)", e);
+  if (!h->d_sens && (e = h->d_sens.alloc(CMPC_SENS_WORDS * B)) != hipSuccess) return fail("hipMalloc(sens)", e);
+  if (!h->d_dtraj && (e = h->d_dtraj.alloc(Stage::kForcesMax * B)) != hipSuccess) return fail("hipMalloc(dtraj)", e);
+  if (!h->d_dg && (e = h->d_dg.alloc(Stage::kForcesMax * B)) != hipSuccess) return fail("hipMalloc(dg)", e);
+  const int N = h->prm.horizon;
+  const size_t rw = (size_t)CMPC_REC_WORDS(N), nf = (size_t)12 * N * batch;
+  if (int r = stream_h2d(h, h->d_rec.get(), records, rw * batch * sizeof(float))) return r;
+  if (int r = stream_h2d(h, h->d_forces.get(), forces, sizeof(float) * nf)) return r;
+  if (int r = stream_h2d(h, h->d_gradf.get(), grad_forces, sizeof(float) * nf)) return r;
+  if (int r = cmpc_batch_sensitivity(h, h->d_rec.get(), h->d_forces.get(), h->d_gradf.get(), batch, act_tol,
+                                     h->d_sens.get(), dtraj ? h->d_dtraj.get() : nullptr,
+                                     dg ? h->d_dg.get() : nullptr))
+    return r;
+  if (int r = stream_d2h(h, sens, h->d_sens.get(), sizeof(double) * CMPC_SENS_WORDS * batch)) return r;
+  if (dtraj)
+    if (int r = stream_d2h(h, dtraj, h->d_dtraj.get(), sizeof(double) * nf)) return r;
+  if (dg)
+    if (int r = stream_d2h(h, dg, h->d_dg.get(), sizeof(double) * nf)) return r;
   return stream_sync(h);
 }
 
@@ -1114,25 +1180,42 @@ void update_x_drag(float x_drag) {
   g.x_drag = x_drag;
 }
 
-extern "C" int cmpc_evaluate_last(float* x_pred, double* cert) {
-  std::lock_guard<std::mutex> lk(g.mu);
+// The record and the forces of the last update_problem_data* call, for cmpc_evaluate_last and
+// cmpc_sensitivity_last (g.mu held): 0, or a negative error with its text set
+static int last_solve(const char* who, std::vector<float>& rec, std::vector<float>& forces) {
   if (!g.has_solved || !g.eval_ok || !g.h) {
-    g_last_error = "cmpc_evaluate_last: no solved update_problem_data* call to evaluate";
+    g_last_error = std::string(who) + ": no solved update_problem_data* call to evaluate";
     return -4;
   }
   // the record as the solve read it (f_est(3) and its flag written by the device estimator step)
   // is still in the handle's staging; the forces are q_soln, which get_solution returns
   const int N = g.h_horizon;
   if ((int)g.q_soln.size() != 12 * N) {
-    g_last_error = "cmpc_evaluate_last: the last solution is of another horizon";
+    g_last_error = std::string(who) + ": the last solution is of another horizon";
     return -4;
   }
-  std::vector<float> rec(CMPC_REC_WORDS(N)), forces(12 * N);
+  rec.resize(CMPC_REC_WORDS(N));
+  forces.resize(12 * N);
   hipError_t e = hipStreamSynchronize(g.h->stream);
   if (e == hipSuccess) e = hipMemcpy(rec.data(), g.h->d_rec.get(), rec.size() * sizeof(float), hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail("D2H", e);
   for (int i = 0; i < 12 * N; i++) forces[i] = (float)g.q_soln[i];
+  return 0;
+}
+
+extern "C" int cmpc_evaluate_last(float* x_pred, double* cert) {
+  std::lock_guard<std::mutex> lk(g.mu);
+  std::vector<float> rec, forces;
+  if (int r = last_solve("cmpc_evaluate_last", rec, forces)) return r;
   return cmpc_batch_evaluate_host(g.h, rec.data(), forces.data(), 1, x_pred, cert);
+}
+
+extern "C" int cmpc_sensitivity_last(const float* grad_forces, double act_tol, double* sens, double* dtraj,
+                                     double* dg) {
+  std::lock_guard<std::mutex> lk(g.mu);
+  std::vector<float> rec, forces;
+  if (int r = last_solve("cmpc_sensitivity_last", rec, forces)) return r;
+  return cmpc_batch_sensitivity_host(g.h, rec.data(), forces.data(), grad_forces, 1, act_tol, sens, dtraj, dg);
 }
 
 extern "C" double get_solution(int index) {

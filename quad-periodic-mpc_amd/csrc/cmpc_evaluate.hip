@@ -22,12 +22,10 @@
 #ifndef CMPC_EVALUATE_INST
 #define CMPC_EVALUATE_INST 0  // 1: the per-instance build (a second unit of this file; see the kernel below)
 #endif
-#include "cmpc_common.h"
+#include "cmpc_rigid64.h"
 
 namespace cmpc {
 namespace {
-
-constexpr int kEvS0 = 32;  // scr: [0..8] R, [9..17] I_world^-1, [18] x_drag, [19] f_est(3) term, [20..31] x_0
 
 struct EvalShared {
   double scr[kEvS0];
@@ -36,38 +34,6 @@ struct EvalShared {
   float u[12 * MAXN];
   float traj[12 * MAXN];
 };
-
-// x_0's rpy exactly as the reference pipeline's restatement evaluates quat_to_rpy
-// (SolverMPC.cpp:352-361): the arguments in fp32 with every product and sum rounded (no fused
-// multiply-add), the inverse trigonometric functions in fp64, the result rounded to fp32.
-__device__ __forceinline__ void rpy_rounded(const float* __restrict__ rec, double* rpy) {
-  const float w = rec[CMPC_REC_Q + 0], x = rec[CMPC_REC_Q + 1], y = rec[CMPC_REC_Q + 2], z = rec[CMPC_REC_Q + 3];
-  const float ww = __fmul_rn(w, w), xx = __fmul_rn(x, x), yy = __fmul_rn(y, y), zz = __fmul_rn(z, z);
-  double asd = -2.0 * (double)__fsub_rn(__fmul_rn(x, z), __fmul_rn(w, y));
-  if (!(asd < .99999)) asd = .99999;  // only the upper clamp, as the reference
-  const float as = (float)asd;
-  const float n0 = __fmul_rn(2.f, __fadd_rn(__fmul_rn(y, z), __fmul_rn(w, x)));
-  const float d0 = __fadd_rn(__fsub_rn(__fsub_rn(ww, xx), yy), zz);
-  const float n2 = __fmul_rn(2.f, __fadd_rn(__fmul_rn(x, y), __fmul_rn(w, z)));
-  const float d2 = __fsub_rn(__fsub_rn(__fadd_rn(ww, xx), yy), zz);
-  rpy[0] = (double)(float)atan2((double)n0, (double)d0);
-  rpy[1] = (double)(float)asin((double)as);
-  rpy[2] = (double)(float)atan2((double)n2, (double)d2);
-}
-
-// NaN-propagating maximum (fmax drops a NaN operand; non-finite input is to show in the result)
-__device__ __forceinline__ double nmax(double a, double b) { return (a > b || a != a) ? a : b; }
-
-__device__ __forceinline__ double bfly_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ double bfly_max(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = nmax(v, __shfl_xor(v, m, 64));
-  return v;
-}
 
 // CMPC_EVALUATE_INST = 1 (this file's second unit in build.py's UNITS): the per-instance build
 // for a handle with a table (cmpc_batch_set_instance_params, _set_instance_costs), a kernel and a launcher of their own
@@ -129,66 +95,16 @@ __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restri
     usq += (double)uv * (double)uv;
   }
   if (lane == 0) {
-    // R (Eigen toRotationMatrix, RobotState.cpp:36) and I_world = R I_body R' (SolverMPC.cpp:593;
-    // I_body = diag(ib0, ib1, ib2), the handle's model; RobotState.h:25 is the default) in fp64
-    // from the fp32 quaternion; the inverse by cofactors
-    const double qw = rec[CMPC_REC_Q + 0], qx = rec[CMPC_REC_Q + 1], qy = rec[CMPC_REC_Q + 2],
-                 qz = rec[CMPC_REC_Q + 3];
-    double R[9];
-    R[0] = 1.0 - 2.0 * (qy * qy + qz * qz); R[1] = 2.0 * (qx * qy - qw * qz); R[2] = 2.0 * (qx * qz + qw * qy);
-    R[3] = 2.0 * (qx * qy + qw * qz); R[4] = 1.0 - 2.0 * (qx * qx + qz * qz); R[5] = 2.0 * (qy * qz - qw * qx);
-    R[6] = 2.0 * (qx * qz - qw * qy); R[7] = 2.0 * (qy * qz + qw * qx); R[8] = 1.0 - 2.0 * (qx * qx + qy * qy);
-    double Iw[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int j = 0; j < 3; j++)
-        Iw[3 * i + j] = R[3 * i] * ib0 * R[3 * j] + R[3 * i + 1] * ib1 * R[3 * j + 1] +
-                        R[3 * i + 2] * ib2 * R[3 * j + 2];
-    const double c00 = Iw[4] * Iw[8] - Iw[5] * Iw[7];
-    const double c10 = Iw[5] * Iw[6] - Iw[3] * Iw[8];
-    const double c20 = Iw[3] * Iw[7] - Iw[4] * Iw[6];
-    const double idet = 1.0 / (Iw[0] * c00 + Iw[1] * c10 + Iw[2] * c20);
-#pragma unroll
-    for (int i = 0; i < 9; i++) scr[i] = R[i];
-    scr[9] = c00 * idet;  scr[10] = (Iw[2] * Iw[7] - Iw[1] * Iw[8]) * idet; scr[11] = (Iw[1] * Iw[5] - Iw[2] * Iw[4]) * idet;
-    scr[12] = c10 * idet; scr[13] = (Iw[0] * Iw[8] - Iw[2] * Iw[6]) * idet; scr[14] = (Iw[2] * Iw[3] - Iw[0] * Iw[5]) * idet;
-    scr[15] = c20 * idet; scr[16] = (Iw[1] * Iw[6] - Iw[0] * Iw[7]) * idet; scr[17] = (Iw[0] * Iw[4] - Iw[1] * Iw[3]) * idet;
-    const uint32_t flags = __float_as_uint(rec[CMPC_REC_FLAGS]);
-    scr[18] = (double)rec[CMPC_REC_XDRAG];
-    scr[19] = (flags & 1u) ? (double)rec[CMPC_REC_FEST3] : 0.0;  // Q_c f (SolverMPC.cpp:808-811)
-    rpy_rounded(rec, &scr[20]);
-#pragma unroll
-    for (int i = 0; i < 3; i++) {
-      scr[23 + i] = (double)rec[CMPC_REC_P + i];
-      scr[26 + i] = (double)rec[CMPC_REC_W + i];
-      scr[29 + i] = (double)rec[CMPC_REC_V + i];
-    }
+    rigid_setup(rec, ib0, ib1, ib2, scr);
   }
   wsync();
 
   // ---- A: per step and axis, sum_f (r_f x u_f)_a and sum_f u_f,a over all four feet
-  if (lane < 3 * N) {
-    const int k = lane / 3, a = lane - 3 * k;
-    const int a1 = (a == 2) ? 0 : a + 1, a2 = (a == 0) ? 2 : a - 1;
-    double tc = 0.0, sc = 0.0;
-#pragma unroll
-    for (int f = 0; f < 4; f++) {
-      const float* uf = &sh.u[12 * k + 3 * f];
-      // (r x u)_a = r_a1 u_a2 - r_a2 u_a1
-      tc += (double)rec[CMPC_REC_R + 4 * a1 + f] * (double)uf[a2] - (double)rec[CMPC_REC_R + 4 * a2 + f] * (double)uf[a1];
-      sc += (double)uf[a];
-    }
-    sh.ts[6 * k + a] = tc;
-    sh.ts[6 * k + 3 + a] = sc;
-  }
+  foot_sums(lane, N, rec, sh.u, sh.ts);
   wsync();
 
   // ---- B: d_k,j = (Bdt u_k + Qdt f)_j + (Adt's column of the gravity state) x0[12]; slot k = N: U = 0
   {
-    const double* R = scr;
-    const double* Ii = scr + 9;
-    const double xd = scr[18];
     const double grav = (double)(-9.8f);  // x0[12] (SolverMPC.cpp:592)
     for (int t = lane; t < 12 * (N + 1); t += 64) {
       const int k = t / 12, j = t - 12 * k;
@@ -200,25 +116,7 @@ __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restri
         tq[i] = zero ? 0.0 : tsk[i];
         sq[i] = zero ? 0.0 : tsk[3 + i];
       }
-      // w = B_c u_k + Q_c f: w[6:9] = I_world^-1 t, w[9:12] = s / m (+ f_est(3) into row 9)
-      const double w9 = sq[0] * im64 + scr[19];
-      double c;
-      if (j < 3 || (j >= 6 && j < 9)) {
-        c = 0.0;
-#pragma unroll
-        for (int m = 0; m < 3; m++) {
-          const double wm = Ii[3 * m] * tq[0] + Ii[3 * m + 1] * tq[1] + Ii[3 * m + 2] * tq[2];
-          c += (j < 3) ? dth * R[3 * m + j] * wm : ((j - 6 == m) ? dt * wm : 0.0);
-        }
-      } else if (j == 3 || j == 9) {
-        c = ((j == 3) ? dth : dt) * w9;
-      } else if (j == 4 || j == 10) {
-        c = ((j == 4) ? dth : dt) * sq[1] * im64;
-      } else if (j == 5) {
-        c = dth * sq[2] * im64 + dt3 * xd * w9 + dth * grav;
-      } else {
-        c = dt * sq[2] * im64 + dth * xd * w9 + dt * grav;
-      }
+      const double c = step_input(j, tq, sq, scr[19], grav, scr, dt, dth, dt3, im64);
       sh.st[t] = c;
     }
   }
@@ -228,19 +126,14 @@ __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restri
   double cacc = 0.0, c0acc = 0.0;
   {
     const int jj = (lane < 12) ? lane : 11;
-    const double* R = scr;
     float wf = 0.f;
 #pragma unroll
     for (int i = 0; i < 12; i++) wf = (jj == i) ? P.wts[i] : wf;
     const double wj = (double)wf;
     // x_j += (N1 x)_j + d_k,j  (N1 = Adt - I: rows 0..2 dt R' x[6:9]; 3, 4 dt x9, x10;
     // 5 dt x11 + dt^2/2 x_drag x9; 11 dt x_drag x9; the gravity state's terms are in d)
-    double c6 = 0.0, c7 = 0.0, c8 = 0.0, c9 = 0.0, c10 = 0.0, c11 = 0.0;
-    if (jj < 3) { c6 = dt * R[jj]; c7 = dt * R[3 + jj]; c8 = dt * R[6 + jj]; }
-    if (jj == 3) c9 = dt;
-    if (jj == 4) c10 = dt;
-    if (jj == 5) { c11 = dt; c9 = dth * scr[18]; }
-    if (jj == 11) c9 = dt * scr[18];
+    const N1Row n1 = n1_row(jj, scr, dt, dth);
+    const double c6 = n1.c6, c7 = n1.c7, c8 = n1.c8, c9 = n1.c9, c10 = n1.c10, c11 = n1.c11;
     double x = scr[20 + jj], x0 = x;
     const double d0 = sh.st[12 * N + jj];
     float* xp = d_xpred ? d_xpred + (size_t)inst * 12 * N : nullptr;
@@ -265,11 +158,8 @@ __global__ __launch_bounds__(64) void cmpc_evaluate_kernel(const float* __restri
     // lambda_j += (N1' lambda)_j + 2 W e  (rows 6..8 dt R lambda[0:3]; 9 dt (l3 + x_drag l11) +
     // dt^2/2 x_drag l5; 10 dt l4; 11 dt l5)
     double lam = 0.0;
-    double e0c = 0.0, e1c = 0.0, e2c = 0.0, e3c = 0.0, e4c = 0.0, e5c = 0.0, e11c = 0.0;
-    if (jj >= 6 && jj < 9) { e0c = dt * R[3 * (jj - 6)]; e1c = dt * R[3 * (jj - 6) + 1]; e2c = dt * R[3 * (jj - 6) + 2]; }
-    if (jj == 9) { e3c = dt; e11c = dt * scr[18]; e5c = dth * scr[18]; }
-    if (jj == 10) e4c = dt;
-    if (jj == 11) e5c = dt;
+    const N1tRow n1t = n1t_row(jj, scr, dt, dth);
+    const double e0c = n1t.e0, e1c = n1t.e1, e2c = n1t.e2, e3c = n1t.e3, e4c = n1t.e4, e5c = n1t.e5, e11c = n1t.e11;
     for (int k = N - 1; k >= 0; k--) {
       const double sk = sh.st[12 * k + jj];
       const double m0 = rl_d(lam, 0), m1 = rl_d(lam, 1), m2 = rl_d(lam, 2), m3 = rl_d(lam, 3);

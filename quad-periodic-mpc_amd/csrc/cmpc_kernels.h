@@ -202,6 +202,14 @@ hipError_t launch_condense(const float* d_recs, int batch, const KParams& P, flo
 hipError_t launch_evaluate(const float* d_recs, const float* d_forces, int batch, const KParams& P,
                            double alpha, const double* ib64, float* d_xpred, double* d_cert,
                            hipStream_t stream, const double* inst_rows = nullptr);
+// the gradients of a loss through the solve at given forces, by an fp64 Riccati adjoint
+// (cmpc_sensitivity.hip), one wavefront per instance. d_gradf = dL/dU [batch x 12N]; alpha, ib64
+// and inst_rows as launch_evaluate's; d_sens [batch x CMPC_SENS_WORDS]; d_dtraj / d_dg [batch x 12N]:
+// either may be NULL
+hipError_t launch_sensitivity(const float* d_recs, const float* d_forces, const float* d_gradf, int batch,
+                              const KParams& P, double alpha, const double* ib64, double act_tol, double* d_sens,
+                              double* d_dtraj, double* d_dg, hipStream_t stream,
+                              const double* inst_rows = nullptr);
 // per-instance table (cmpc_inst_table.hip). check: *d_bad += the number of rows that
 // cmpc_batch_set_model or cmpc_batch_set_params would refuse (d_bad zeroed by the caller);
 // convert: the kernel-side entries and the snapshot of the rows, formed as make_kmodel and

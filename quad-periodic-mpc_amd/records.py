@@ -33,6 +33,10 @@ EST_WORDS = 816
 # words of a certificate row of BatchSolver.evaluate (CMPC_CERT_* of include/cmpc_solver.h)
 CERT_COST, CERT_COST0, CERT_GAP, CERT_VIOL, CERT_SWING, CERT_GRADMAX = range(6)
 CERT_WORDS = 8
+# words of a row of BatchSolver.sensitivity (CMPC_SENS_* of include/cmpc_solver.h): dL/dx_0 [12],
+# dL/dweights [12], dL/dalpha, dL/df_est(3), the face's dimension, the smallest inactive slack
+SENS_X0, SENS_WEIGHTS, SENS_ALPHA, SENS_FEST3, SENS_FREE, SENS_SLACK = 0, 12, 24, 25, 26, 27
+SENS_WORDS = 32
 
 STATUS_NAMES = {0: "ok", 1: "max_iter", 2: "infeasible", 3: "not_pd", 4: "bad_input"}
 # locomotion-controller state for batched input assembly (include/cmpc_solver.h CMPC_LOCO_*)

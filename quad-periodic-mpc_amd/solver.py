@@ -24,6 +24,8 @@ from .records import INST_WORDS, make_instance_params  # noqa: F401
 from .records import COST_WORDS, make_instance_costs  # noqa: F401
 from .records import (CERT_COST, CERT_COST0, CERT_GAP, CERT_VIOL, CERT_SWING, CERT_GRADMAX,  # noqa: F401
                       CERT_WORDS, MAX_HORIZON)
+from .records import (SENS_X0, SENS_WEIGHTS, SENS_ALPHA, SENS_FEST3, SENS_FREE, SENS_SLACK,  # noqa: F401
+                      SENS_WORDS)
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CMPC_LIB", os.path.join(PKG, "libcmpc_hip.so"))
@@ -87,6 +89,9 @@ _PROTOTYPES = {
     "cmpc_batch_evaluate": (_int, [_vp, _vp, _vp, _int, _vp, _vp]),
     "cmpc_batch_evaluate_host": (_int, [_vp, _fp, _fp, _int, _fp, _dp]),
     "cmpc_evaluate_last": (_int, [_fp, _dp]),
+    "cmpc_batch_sensitivity": (_int, [_vp, _vp, _vp, _vp, _int, _dbl, _vp, _vp, _vp]),
+    "cmpc_batch_sensitivity_host": (_int, [_vp, _fp, _fp, _fp, _int, _dbl, _dp, _dp, _dp]),
+    "cmpc_sensitivity_last": (_int, [_fp, _dbl, _dp, _dp, _dp]),
     "cmpc_batch_enable_timing": (_int, [_vp, _int]),
     "cmpc_batch_enable_timing_every": (_int, [_vp, _int, _int]),
     "cmpc_batch_read_timing": (_int, [_vp, _fp, _ip, _ip]),
@@ -202,6 +207,22 @@ def evaluate_last():
     _check(lib.cmpc_evaluate_last(x_pred.ctypes.data_as(_fp), cert.ctypes.data_as(_dp)),
            "cmpc_evaluate_last")
     return x_pred[:12 * _setup_horizon].reshape(-1, 12).copy(), cert
+
+
+def sensitivity_last(grad_forces, act_tol: float = 1e-3):
+    """``cmpc_sensitivity_last``: the gradients of a loss through the last ``update_problem_data*``
+    call's solve, from ``grad_forces`` = dL/dU [12N] -> (sens [SENS_WORDS], dtraj [N, 12],
+    dg [12N]), all float64. Runs on request only; raises before the first solve."""
+    lib = load_library()
+    n = 12 * _setup_horizon
+    v = _f32(grad_forces, n)
+    sens = np.zeros(SENS_WORDS, np.float64)
+    dtraj = np.zeros(12 * MAX_HORIZON, np.float64)
+    dg = np.zeros(12 * MAX_HORIZON, np.float64)
+    _check(lib.cmpc_sensitivity_last(v.ctypes.data_as(_fp), float(act_tol), sens.ctypes.data_as(_dp),
+                                     dtraj.ctypes.data_as(_dp), dg.ctypes.data_as(_dp)),
+           "cmpc_sensitivity_last")
+    return sens, dtraj[:n].reshape(-1, 12).copy(), dg[:n].copy()
 
 
 def set_f_ext(values) -> None:
@@ -448,6 +469,52 @@ class BatchSolver:
                                                  x_pred.ctypes.data_as(_fp), cert.ctypes.data_as(_dp)),
                "cmpc_batch_evaluate_host")
         return x_pred, cert
+
+    def sensitivity(self, records, forces, grad_forces, sens, dtraj=None, dg=None, act_tol: float = 1e-3,
+                    batch: int | None = None) -> None:
+        """Gradients of a loss through the solve by the fp64 Riccati adjoint
+        (``cmpc_batch_sensitivity``; asynchronous on the handle's stream): ``forces`` and
+        ``grad_forces`` = dL/dU are [B, 12N] float32 on device, ``sens`` [B, SENS_WORDS] float64 is
+        the output (indexed by ``SENS_*``), ``dtraj`` (dL/d trajectory) and ``dg`` (the adjoint w)
+        are optional [B, 12N] float64 outputs. A row is active when its slack is at most ``act_tol``
+        newtons. Checked as :meth:`evaluate` checks its arguments."""
+        if batch is None:
+            batch = records.shape[0]
+        if batch > self.max_batch:
+            raise CmpcError(f"batch {batch} > max_batch {self.max_batch}")
+        n = 12 * self.horizon
+        if hasattr(records, "shape"):
+            assert records.shape[-1] == self.record_words, "record stride mismatch"
+        for name, t in (("forces", forces), ("grad_forces", grad_forces)):
+            if hasattr(t, "numel"):
+                assert t.dtype.is_floating_point and t.element_size() == 4, f"{name} must be float32"
+                assert t.numel() >= batch * n
+        for name, t, words in (("sens", sens, SENS_WORDS), ("dtraj", dtraj, n), ("dg", dg, n)):
+            if hasattr(t, "numel"):
+                assert t.element_size() == 8 and t.dtype.is_floating_point, f"{name} must be float64"
+                assert t.numel() >= batch * words
+        _check(self.lib.cmpc_batch_sensitivity(self._h, _ptr(records), _ptr(forces), _ptr(grad_forces),
+                                               int(batch), float(act_tol), _ptr(sens), _ptr(dtraj), _ptr(dg)),
+               "cmpc_batch_sensitivity")
+
+    def sensitivity_host(self, records: np.ndarray, forces: np.ndarray, grad_forces: np.ndarray,
+                         act_tol: float = 1e-3, dtraj: bool = True, dg: bool = True):
+        """Host arrays in/out (H2D + kernel + D2H, synchronous) -> (sens [B, SENS_WORDS],
+        dtraj [B, N, 12] or None, dg [B, 12N] or None), float64."""
+        records = np.ascontiguousarray(records, np.float32)
+        forces = np.ascontiguousarray(forces, np.float32)
+        grad_forces = np.ascontiguousarray(grad_forces, np.float32)
+        B, n = records.shape[0], 12 * self.horizon
+        assert records.shape[1] == self.record_words and forces.size == B * n and grad_forces.size == B * n
+        sens = np.zeros((B, SENS_WORDS), np.float64)
+        o_traj = np.zeros((B, self.horizon, 12), np.float64) if dtraj else None
+        o_dg = np.zeros((B, n), np.float64) if dg else None
+        _check(self.lib.cmpc_batch_sensitivity_host(
+            self._h, records.ctypes.data_as(_fp), forces.ctypes.data_as(_fp), grad_forces.ctypes.data_as(_fp),
+            B, float(act_tol), sens.ctypes.data_as(_dp),
+            o_traj.ctypes.data_as(_dp) if dtraj else None, o_dg.ctypes.data_as(_dp) if dg else None),
+            "cmpc_batch_sensitivity_host")
+        return sens, o_traj, o_dg
 
     def condense(self, records, H, g, batch: int | None = None, rows: bool = False) -> None:
         """Full (no elimination) qH [B,12N,12N] / qg [B,12N] on device — parity hook.
