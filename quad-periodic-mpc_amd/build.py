@@ -179,7 +179,7 @@ def build_plan_dump() -> str:
 
 def build_mfma_probe() -> str:
     """cmpc_mfma_probe: a stand-alone one-wave check of the broadcast 4x4x1 MFMA's register layout
-    and rounding, which the class-1 row sweeps (mfma_chunk in cmpc_class1.hip) rely on."""
+    and rounding, which the class-1 and tail-class row sweeps (mfma_chunk in cmpc_common.h) rely on."""
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     exe = os.path.join(PKG, "cmpc_mfma_probe")
     src = os.path.join(CSRC, "tools", "cmpc_mfma_probe.cpp")

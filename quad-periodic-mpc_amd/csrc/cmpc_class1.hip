@@ -156,28 +156,9 @@ __device__ __forceinline__ void lsync() {
 
 __device__ __forceinline__ float fdiv(float a, float b) { return a * fast_rcp(b); }
 
-// Row sweeps as broadcast outer products on the matrix pipe (v_mfma_f32_4x4x1_16b_f32, cbsz 4):
-// every sweep FMA is slot[c] += (this lane's coefficient) x (a value lane c holds), and with
-// A = the lane-natural column register, B = the coefficient and abid = c / 4 one MFMA does
-//   slot[c + i] (lane v) += A(lane c + i) B(lane v),  i = 0..3,
-// a whole sweep chunk with no LDS broadcast and no VALU FMA (layout and rounding checked by
-// tools/cmpc_mfma_probe.cpp). MFMAs ignore EXEC: each sits in wave-uniform control flow.
-// The MFMA rounds as one fmaf, denormals included, and each sweep keeps every element's order of
-// additions. Two sweeps run this way: the Cholesky's rank-2 trailing sweep and the active set's
-// reflection update (profiles/r12_mfma).
-typedef float f4m __attribute__((ext_vector_type(4)));
-// one sweep chunk: x_i (this lane) += col(lane C + i) * coef (this lane), i = 0..3 (C = 0 mod 4)
-template <int C>
-__device__ __forceinline__ void mfma_chunk(float col, float coef, float& x0, float& x1, float& x2,
-                                           float& x3) {
-  static_assert((C & 3) == 0 && C >= 0 && C < 64, "chunk start");
-  f4m acc = {x0, x1, x2, x3};
-  acc = __builtin_amdgcn_mfma_f32_4x4x1f32(col, coef, acc, 4, C / 4, 0);
-  x0 = acc[0];
-  x1 = acc[1];
-  x2 = acc[2];
-  x3 = acc[3];
-}
+// The row sweeps run as broadcast MFMA outer products (mfma_chunk, cmpc_common.h). Two sweeps run
+// this way here: the Cholesky's rank-2 trailing sweep and the active set's reflection update
+// (profiles/r12_mfma).
 
 // Register pin: forces every row element to be materialised at this point. Without it LLVM sinks
 // the right-looking updates of slot[c] down to the step that first reads slot[c] (turning the

@@ -164,7 +164,11 @@ __device__ __forceinline__ float tail_alpha2(const KParams& P, int inst) {
 // INST: the per-instance build (cmpc_batch_set_instance_params, _set_instance_costs): the model,
 // f_max, 1 / mu, the weights and 2 alpha from the instance's table entry P.inst[inst] (scalar
 // loads, inst_late) instead
-template <int T, int POFF, bool INST = false>
+// MSWEEP: the sweeps over the main columns in the main pivots and in the J pass as MFMA outer
+// products. Every build but the looping per-instance one, whose scratch they took from 40 to 48 - 52 B
+// per lane; that build keeps the broadcast reads and VALU FMAs and computes the same bits (mfma_chunk
+// rounds as the fmaf it replaces, and every element keeps its order of additions)
+template <int T, int POFF, bool INST = false, bool MSWEEP = true>
 __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KParams& P,
                                         SharedT<T>& sh, float* __restrict__ fout,
                                         uint8_t* __restrict__ st_out, int32_t* __restrict__ it_out,
@@ -397,10 +401,15 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
   // k / k+1). The tail parts (rows 64..NV-1) of a pivot pair's columns are the registers 64..NV-1
   // of lanes k and k+1, stored raw by those lanes once the previous step's sweep has updated them
   // (the tail chunks are the last of every sweep); the tail chunks and the tail block apply them
-  // with the raw-column coefficients (a0 - beta a1, a1).
+  // with the raw-column coefficients (a0 - beta a1, a1). The main chunks take the two columns from
+  // the registers look leaves them in, as MFMA outer products (round 22); the tail chunks have no
+  // lane of their own and stay on the LDS path.
   int status = CMPC_OK;
   float my_inv = 1.f;
   float i0n = 1.f, betan = 0.f, i1n = 1.f, g0n = 0.f, g1n = 0.f;
+  // the two published columns as look leaves them, one element per lane: the A operand of the main
+  // columns' sweep (mfma_chunk), which takes lane c's element where the LDS path broadcast P[c]
+  float pub0n = 0.f, pub1n = 0.f;
   auto look = [&](auto JJ) {
     constexpr int j = decltype(JJ)::value, j1 = j + 1;
     constexpr int cj = j & ~3, cj1 = j1 & ~3;
@@ -416,8 +425,11 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
       g0n = rl(slot[NV], j);
       g1n = fmaf(-betan, g0n, rl(slot[NV], j1));
       const float s1 = fmaf(-slot[j], betan, slot[j1]);
-      if (v >= cj) sh.P[G::prow(j) + v - cj] = (v >= j) ? slot[j] : 0.f;
-      if (v >= cj1) sh.P[G::prow(j1) + v - cj1] = (v >= j1) ? s1 : 0.f;
+      // (the stores feed the J pass, and the tail chunks' raw parts below)
+      pub0n = (v >= j) ? slot[j] : 0.f;
+      pub1n = (v >= j1) ? s1 : 0.f;
+      if (v >= cj) sh.P[G::prow(j) + v - cj] = pub0n;
+      if (v >= cj1) sh.P[G::prow(j1) + v - cj1] = pub1n;
       tsync();
     }
   };
@@ -455,15 +467,40 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
     const float a0 = (v > k) ? -s0 * (i0 * i0) : 0.f;
     const float a1 = (v > k1) ? -s1 * (i1 * i1) : 0.f;
     slot[NV] = fmaf(a1, g1, fmaf(a0, g0, slot[NV]));
-    static_for<c2 / 4, 16>([&](auto JC) {
-      constexpr int c = 4 * decltype(JC)::value;
-      const float4 r0 = *reinterpret_cast<const float4*>(&sh.P[rk + c - c0]);
-      const float4 r1 = *reinterpret_cast<const float4*>(&sh.P[rk1 + c - c1]);
-      axpy4(a0, r0, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
-      axpy4(a1, r1, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
-      if constexpr (k2 < 64 && c == c2) look(std::integral_constant<int, k2>{});
-      CMPC_TSWEEP_FENCE(c);
-    });
+    // the main columns, slot[c] += a0 P_k[c] + a1 P_k+1[c] with P[c] taken from lane c's published
+    // register as MFMA outer products (cmpc_common.h, mfma_chunk; class 1's round-12 form): no LDS
+    // broadcast, no VALU FMA, each element's two FMAs in pivot order as before. The chunk that holds
+    // the next pair's columns takes both pivots first and look(k+2) follows it at once; the other
+    // chunks all of pivot k, then all of pivot k+1 (two MFMAs on one accumulator a sweep apart).
+    // Straight-line code over the 64 main pivots: wave-uniform, as the MFMAs need (they ignore EXEC).
+    // A build with MSWEEP = false keeps the broadcast reads of the stored columns and VALU FMAs: the
+    // same values in the same order, bit for bit.
+    if constexpr (MSWEEP) {
+      const float p0 = pub0n, p1 = pub1n;
+      if constexpr (c2 < 64) {
+        mfma_chunk<c2>(p0, a0, slot[c2 + 0], slot[c2 + 1], slot[c2 + 2], slot[c2 + 3]);
+        mfma_chunk<c2>(p1, a1, slot[c2 + 0], slot[c2 + 1], slot[c2 + 2], slot[c2 + 3]);
+        if constexpr (k2 < 64) look(std::integral_constant<int, k2>{});
+      }
+      static_for<c2 / 4 + 1, 16>([&](auto JC) {
+        constexpr int c = 4 * decltype(JC)::value;
+        mfma_chunk<c>(p0, a0, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
+      });
+      static_for<c2 / 4 + 1, 16>([&](auto JC) {
+        constexpr int c = 4 * decltype(JC)::value;
+        mfma_chunk<c>(p1, a1, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
+      });
+    } else {
+      static_for<c2 / 4, 16>([&](auto JC) {
+        constexpr int c = 4 * decltype(JC)::value;
+        const float4 r0 = *reinterpret_cast<const float4*>(&sh.P[rk + c - c0]);
+        const float4 r1 = *reinterpret_cast<const float4*>(&sh.P[rk1 + c - c1]);
+        axpy4(a0, r0, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
+        axpy4(a1, r1, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
+        if constexpr (k2 < 64 && c == c2) look(std::integral_constant<int, k2>{});
+        CMPC_TSWEEP_FENCE(c);
+      });
+    }
     // materialise the main columns here: otherwise the FMAs sink below the divergent stores that
     // follow (IR-level sinking toward the step's pin) and every loaded chunk stays live (800 spills)
     tpin(slot);
@@ -563,7 +600,7 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
       const float x0 = slot[k] * i0;
       const float x1 = fmaf(-h * i0, x0, slot[k1]) * i1;
       const float a0 = -x0 * i0, a1 = -x1 * i1;
-      if constexpr (c2 < 64) {
+      if constexpr (c2 < 64 && !MSWEEP) {
 #pragma unroll
         for (int c = c2; c < 64; c += 4) {
           const float4 r0 = *reinterpret_cast<const float4*>(&sh.P[rk + c - c0]);
@@ -572,6 +609,21 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
           axpy4(a1, r1, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
           CMPC_TSWEEP_FENCE(c);
         }
+      }
+      if constexpr (c2 < 64 && MSWEEP) {
+        // the main columns as MFMA outer products (mfma_chunk): the stored columns k, k+1 read back
+        // one element per lane, which is what the broadcast reads gave every lane of element c; all
+        // of column k, then all of column k+1, each element's two FMAs in the order they had
+        const float q0 = (v >= c0) ? sh.P[rk + v - c0] : 0.f;
+        const float q1 = (v >= c1) ? sh.P[rk1 + v - c1] : 0.f;
+        static_for<c2 / 4, 16>([&](auto JC) {
+          constexpr int c = 4 * decltype(JC)::value;
+          mfma_chunk<c>(q0, a0, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
+        });
+        static_for<c2 / 4, 16>([&](auto JC) {
+          constexpr int c = 4 * decltype(JC)::value;
+          mfma_chunk<c>(q1, a1, slot[c + 0], slot[c + 1], slot[c + 2], slot[c + 3]);
+        });
       }
       const float a0t = (k < 64) ? fmaf(-sh.u.ch.bpair[k / 2], a1, a0) : a0;
 #pragma unroll
@@ -887,7 +939,9 @@ __device__ __forceinline__ void solve_t(const float* __restrict__ rec, const KPa
       }
       tsync();
       {
-        // J <- J (I - beta w w') (no-op on a drop: beta = 0)
+        // J <- J (I - beta w w') (no-op on a drop: beta = 0). (The update stays on the broadcast reads:
+        // as MFMA outer products, w[v] in a register or read back from vbuf alike, it took scratch
+        // from 24 / 48 to 32 / 108 B per lane, profiles/r22_tail/registers.md)
         f2v tacc = {0.f, 0.f};
         piped_sweep<0, NV, TAIL_PIPE_GRP>(
             [&](auto C) { return *reinterpret_cast<const float4*>(&sh.vbuf()[decltype(C)::value]); },
@@ -1065,8 +1119,9 @@ __global__ __launch_bounds__(64, CMPC_TAIL_WAVES_PER_EU) void cmpc_solve_t_rest_
   const int count = *in_count;
   for (int b = first + (int)blockIdx.x; b < count; b += (int)gridDim.x) {
     const int t = in_list[b];
-    solve_t<kTailRows, KP::offset(), true>(recs + (size_t)t * P.rec_words, P, sh, forces + (size_t)t * P.out_cols,
-                                           status + t, iters ? iters + t : nullptr, ovf_list, ovf_count, t);
+    solve_t<kTailRows, KP::offset(), true, false>(recs + (size_t)t * P.rec_words, P, sh,
+                                                  forces + (size_t)t * P.out_cols, status + t,
+                                                  iters ? iters + t : nullptr, ovf_list, ovf_count, t);
     __builtin_amdgcn_wave_barrier();
     asm volatile("" ::: "memory");
   }
