@@ -476,6 +476,72 @@ CMPC_EXTERNC int cmpc_batch_sensitivity_host(cmpc_batch* h, const float* records
  * NULL). Runs on request only. Returns a negative error before the first solve. New API. */
 CMPC_EXTERNC int cmpc_sensitivity_last(const float* grad_forces, double act_tol, double* sens,
                                        double* dtraj, double* dg);
+/* The step-0 feedback gain of the solve: given forces U [batch * 12N] (any source, as for
+ * cmpc_batch_evaluate), G = d u_0* / d x_0 [12 x 12], with which a controller that holds the solved
+ * forces for iters_between_mpc ticks corrects them for the state's drift, u = u_0 + G (x - x_0)
+ * (cmpc_batch_feedback below). The QP, x_0, 1/mu, ub and the stance test are cmpc_batch_evaluate's;
+ * the face, Z_k, the apex rule and the pinned swing foot-steps are cmpc_batch_sensitivity's, word for
+ * word, with act_tol in newtons. New API.
+ * Backwards from P = 0 over the 12 dynamic states, with Pn = P_k+1 + W and G_k = Bdt Z_k:
+ *   R   = alpha Z_k'Z_k + G_k'Pn G_k
+ *   P_k = Adt'Pn Adt - (Adt'Pn G_k) R^-1 (G_k'Pn Adt)
+ *   at k = 0:  K_0 = R^-1 G_0'Pn Adt,  G = -Z_0 K_0
+ * (the backward half of cmpc_batch_sensitivity's recursion, without its upstream gradient, forward
+ * pass or trajectory; one vector-Jacobian product of that call gives one row's worth of G). G is
+ * row-major: row = force component leg*3+axis of step 0, column = component of x_0 in the order of
+ * the traj rows (rpy, p, w, v). G is the derivative of the step-0 forces of the minimiser over U's
+ * face with respect to x_0.
+ *   Validity: as for cmpc_batch_sensitivity: G equals the derivative of the solve where U is the
+ *     optimum and no active row has a zero multiplier; at a weakly active row it is one side's
+ *     derivative, undetected (CMPC_GAIN_SLACK tells how near an inactive row is).
+ *   rpy columns: the partial derivative at a fixed rotation matrix and fixed foot offsets r.
+ *   Rows of swing or pinned foot-steps are exactly +0.0. For an active row with normal n of a step-0
+ *     foot-step, n'G_foot = 0 to rounding.
+ *   G does not depend on the trajectory, p, v, w, f_est(3) or the flag word: those words are not
+ *     read, so NaN there changes no bit.
+ *   Non-finite forces give NaN in words 0..143 and CMPC_GAIN_SLACK, with FREE and FREE0 as
+ *     classified. An instance whose forces are all zero (a failed status) has G = 0 and FREE = 0.
+ * Output: d_gain [batch * CMPC_GAIN_WORDS] fp64. Honours the handle's model and both per-instance
+ * tables as cmpc_batch_evaluate does. Asynchronous on the handle's stream; neither allocates nor
+ * synchronises. Returns 0 or a negative error, those of cmpc_batch_sensitivity: bad batch (beyond
+ * max_batch or a table's count), a NULL argument, a handle that keeps fewer than N output steps
+ * (-3), and -2 for an act_tol that is negative or not finite.
+ * Out of scope: d u_k / d x_0 for k >= 1; gains with respect to the trajectory or f_est; the
+ * derivative through R, r, x_drag, mass, inertia, mu, f_max or dt. */
+#define CMPC_GAIN_K        0    /* 144: G, row-major [force component of step 0][component of x_0] */
+#define CMPC_GAIN_FREE     144  /* m, the face's dimension over all steps, as CMPC_SENS_FREE        */
+#define CMPC_GAIN_FREE0    145  /* the dimension of step 0's face, 0..12                             */
+#define CMPC_GAIN_SLACK    146  /* as CMPC_SENS_SLACK                                                */
+#define CMPC_GAIN_WORDS    148  /* 147 written as 0 */
+CMPC_EXTERNC int cmpc_batch_gain(cmpc_batch* h, const float* d_records, const float* d_forces, int batch,
+                                 double act_tol, double* d_gain);
+/* Same, host buffers in and out (H2D + kernel + D2H on the handle's stream, synchronous). */
+CMPC_EXTERNC int cmpc_batch_gain_host(cmpc_batch* h, const float* records, const float* forces, int batch,
+                                      double act_tol, double* gain);
+/* Single-instance surface: cmpc_batch_gain of the record, the solution and the model of the last
+ * update_problem_data* call (gain [CMPC_GAIN_WORDS]). Runs on request only. Returns a negative error
+ * before the first solve. New API. */
+CMPC_EXTERNC int cmpc_gain_last(double act_tol, double* gain);
+/* The held forces corrected for the present state. d_forces: the solved forces at the handle's
+ * output stride (cmpc_batch_set_output_steps; step 0 alone is read); d_gain: cmpc_batch_gain's
+ * output for them, 16-byte aligned (the rows of G are read by 16-byte loads; the 1184-byte stride of an
+ * instance keeps every row so); d_states [batch * 12] fp32: the present state in the order of the traj rows (what
+ * CMPC_LOCO_RPY / POS / WW / VW hold); d_due [batch] bytes or NULL; d_u [batch * 12] fp32. For
+ * instance i with d_due == NULL or d_due[i] == 0, all in fp64:
+ *   delta = x - x_0 (x_0 as the solve forms it from the record), the three rpy differences wrapped
+ *           by delta - 2 pi rint(delta / 2 pi);
+ *   u     = u_0 + G delta, summed over the columns 0..11 in order;
+ *   guard, per foot of step 0: stance (|ub| >= 0.01): fz <- min(max(fz, 0), ub), then fx, fy clamped
+ *           to +-mu fz with mu = 1 / (the fp32 1/mu); swing: +0.0;
+ *   and one rounding to fp32.
+ * An instance with d_due[i] != 0 has just been solved: its row of d_u is not written and nothing
+ * of it but the due byte is read, so cmpc_batch_assemble's due mask can be passed as it is. Honours
+ * the per-instance parameter table (mu, f_max) as cmpc_batch_evaluate does. Asynchronous on the
+ * handle's stream; neither allocates nor synchronises. Returns 0 or a negative error: bad batch, a
+ * NULL argument other than d_due, a d_gain that is not 16-byte aligned. New API. */
+CMPC_EXTERNC int cmpc_batch_feedback(cmpc_batch* h, const float* d_records, const float* d_forces,
+                                     const double* d_gain, const float* d_states, const uint8_t* d_due,
+                                     int batch, float* d_u);
 /* Single-instance surface: the robot model from the next update_problem_data* call on, as
  * update_solver_settings sets its settings (m == NULL: the default; -2 and no change for a
  * non-finite or non-positive field). cmpc_evaluate_last evaluates under the model of the solve it

@@ -42,10 +42,10 @@ UNITS = ([("cmpc_tail.hip", ()), ("cmpc_class1.hip", ())] +
          [wide_unit(r) for r in sorted(wide_builds(), key=lambda r: -r[0])] +
          [("cmpc_condense.hip", ()), ("cmpc_launch.hip", ()), ("cmpc_inst_table.hip", ()),
           ("cmpc_estimator.hip", ()), ("cmpc_assemble.hip", ()), ("cmpc_admm.hip", ()), ("cmpc_quadprog.hip", ()),
-          ("cmpc_evaluate.hip", ()), ("cmpc_sensitivity.hip", ()),
+          ("cmpc_evaluate.hip", ()), ("cmpc_sensitivity.hip", ()), ("cmpc_gain.hip", ()),
           # the per-instance builds of the hooks, each kernel in a unit of its own
           ("cmpc_condense.hip", ("CMPC_CONDENSE_INST=1",)), ("cmpc_evaluate.hip", ("CMPC_EVALUATE_INST=1",)),
-          ("cmpc_sensitivity.hip", ("CMPC_SENSITIVITY_INST=1",)),
+          ("cmpc_sensitivity.hip", ("CMPC_SENSITIVITY_INST=1",)), ("cmpc_gain.hip", ("CMPC_GAIN_INST=1",)),
           ("cmpc_abi.cpp", ())])
 ARCH = os.environ.get("CMPC_OFFLOAD_ARCH", "gfx950")
 # -fno-slp-vectorize: the SLP pass packs adjacent row updates into v_pk_fma_f32, which ties

@@ -97,6 +97,8 @@ struct __attribute__((visibility("hidden"))) cmpc_batch {
   // input and outputs of cmpc_batch_sensitivity_host (likewise)
   DevBuf<float> d_gradf;
   DevBuf<double> d_sens, d_dtraj, d_dg;
+  // output of cmpc_batch_gain_host (likewise)
+  DevBuf<double> d_gain;
   // side streams + fork/join events for the wider size classes (cmpc_launch.hip)
   cmpc::LaunchCtx ctx;
   PinBuf<int> h_hint;            // ctx.h_hint: freed after the own stream is idle (cmpc_batch_destroy)
@@ -916,6 +918,60 @@ extern "C" int cmpc_batch_sensitivity_host(cmpc_batch* h, const float* records, 
   return stream_sync(h);
 }
 
+// what both gain entry points ask of their arguments: sensitivity's checks without its gradient
+static int gain_check(const char* who, const cmpc_batch* h, int batch, const void* records, const void* forces,
+                      double act_tol, const void* gain) {
+  if (!gain) {
+    g_last_error = std::string(who) + ": gain is NULL";
+    return -1;
+  }
+  if (int r = evaluate_check(who, h, batch, records, forces, gain, gain, ", its forces are not a full solution"))
+    return r;
+  if (!std::isfinite(act_tol) || act_tol < 0.0) {
+    g_last_error = std::string(who) + ": act_tol is negative or not finite";
+    return -2;
+  }
+  return 0;
+}
+
+extern "C" int cmpc_batch_gain(cmpc_batch* h, const float* d_records, const float* d_forces, int batch,
+                               double act_tol, double* d_gain) {
+  if (int r = gain_check("cmpc_batch_gain", h, batch, d_records, d_forces, act_tol, d_gain)) return r;
+  return checked("launch_gain",
+                 cmpc::launch_gain(d_records, d_forces, batch, h->kp, (double)h->prm.alpha, h->model.inertia, act_tol,
+                                   d_gain, h->stream, h->d_inst_rows.get()));
+}
+
+extern "C" int cmpc_batch_gain_host(cmpc_batch* h, const float* records, const float* forces, int batch,
+                                    double act_tol, double* gain) {
+  if (int r = gain_check("cmpc_batch_gain_host", h, batch, records, forces, act_tol, gain)) return r;
+  if (batch == 0) return 0;
+  if (int r = ensure_staging(h)) return r;
+  hipError_t e;
+  if (!h->d_gain && (e = h->d_gain.alloc(CMPC_GAIN_WORDS * (size_t)h->max_batch)) != hipSuccess)
+    return fail("hipMalloc(gain)", e);
+  const int N = h->prm.horizon;
+  const size_t rw = (size_t)CMPC_REC_WORDS(N);
+  if (int r = stream_h2d(h, h->d_rec.get(), records, rw * batch * sizeof(float))) return r;
+  if (int r = stream_h2d(h, h->d_forces.get(), forces, sizeof(float) * 12 * N * batch)) return r;
+  if (int r = cmpc_batch_gain(h, h->d_rec.get(), h->d_forces.get(), batch, act_tol, h->d_gain.get())) return r;
+  if (int r = stream_d2h(h, gain, h->d_gain.get(), sizeof(double) * CMPC_GAIN_WORDS * batch)) return r;
+  return stream_sync(h);
+}
+
+extern "C" int cmpc_batch_feedback(cmpc_batch* h, const float* d_records, const float* d_forces,
+                                   const double* d_gain, const float* d_states, const uint8_t* d_due, int batch,
+                                   float* d_u) {
+  if (!h || !batch_ok(h, batch) || (batch && (!d_records || !d_forces || !d_gain || !d_states || !d_u)))
+    return bad_arguments("cmpc_batch_feedback");
+  if (reinterpret_cast<uintptr_t>(d_gain) % 16 != 0) {
+    g_last_error = "cmpc_batch_feedback: d_gain is not 16-byte aligned";
+    return -1;
+  }
+  return checked("launch_feedback", cmpc::launch_feedback(d_records, d_forces, d_gain, d_states, d_due, batch, h->kp,
+                                                          d_u, h->stream));
+}
+
 // =============================================================================================
 // Reference single-instance interface (convexMPC_interface.cpp + the solve_mpc globals).
 // =============================================================================================
@@ -1180,8 +1236,8 @@ void update_x_drag(float x_drag) {
   g.x_drag = x_drag;
 }
 
-// The record and the forces of the last update_problem_data* call, for cmpc_evaluate_last and
-// cmpc_sensitivity_last (g.mu held): 0, or a negative error with its text set
+// The record and the forces of the last update_problem_data* call, for cmpc_evaluate_last,
+// cmpc_sensitivity_last and cmpc_gain_last (g.mu held): 0, or a negative error with its text set
 static int last_solve(const char* who, std::vector<float>& rec, std::vector<float>& forces) {
   if (!g.has_solved || !g.eval_ok || !g.h) {
     g_last_error = std::string(who) + ": no solved update_problem_data* call to evaluate";
@@ -1216,6 +1272,13 @@ extern "C" int cmpc_sensitivity_last(const float* grad_forces, double act_tol, d
   std::vector<float> rec, forces;
   if (int r = last_solve("cmpc_sensitivity_last", rec, forces)) return r;
   return cmpc_batch_sensitivity_host(g.h, rec.data(), forces.data(), grad_forces, 1, act_tol, sens, dtraj, dg);
+}
+
+extern "C" int cmpc_gain_last(double act_tol, double* gain) {
+  std::lock_guard<std::mutex> lk(g.mu);
+  std::vector<float> rec, forces;
+  if (int r = last_solve("cmpc_gain_last", rec, forces)) return r;
+  return cmpc_batch_gain_host(g.h, rec.data(), forces.data(), 1, act_tol, gain);
 }
 
 extern "C" double get_solution(int index) {

@@ -210,6 +210,17 @@ hipError_t launch_sensitivity(const float* d_recs, const float* d_forces, const 
                               const KParams& P, double alpha, const double* ib64, double act_tol, double* d_sens,
                               double* d_dtraj, double* d_dg, hipStream_t stream,
                               const double* inst_rows = nullptr);
+// the step-0 feedback gain d u_0* / d x_0 at given forces, by the backward half of that recursion
+// (cmpc_gain.hip), one wavefront per instance; alpha, ib64, act_tol and inst_rows as
+// launch_sensitivity's; d_gain [batch x CMPC_GAIN_WORDS]
+hipError_t launch_gain(const float* d_recs, const float* d_forces, int batch, const KParams& P, double alpha,
+                       const double* ib64, double act_tol, double* d_gain, hipStream_t stream,
+                       const double* inst_rows = nullptr);
+// u = guard(u_0 + G (x - x_0)) of every instance that is not due (cmpc_gain.hip): d_forces at the
+// stride P.out_cols, d_states and d_u [batch x 12] fp32, d_due [batch] bytes or NULL; with P.inst,
+// entry i's 1 / mu and f_max
+hipError_t launch_feedback(const float* d_recs, const float* d_forces, const double* d_gain, const float* d_states,
+                           const uint8_t* d_due, int batch, const KParams& P, float* d_u, hipStream_t stream);
 // per-instance table (cmpc_inst_table.hip). check: *d_bad += the number of rows that
 // cmpc_batch_set_model or cmpc_batch_set_params would refuse (d_bad zeroed by the caller);
 // convert: the kernel-side entries and the snapshot of the rows, formed as make_kmodel and

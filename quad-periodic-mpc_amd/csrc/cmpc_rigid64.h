@@ -1,5 +1,5 @@
 // cmpc_rigid64.h — what the fp64 kernels of one wavefront per instance share (cmpc_evaluate.hip,
-// cmpc_sensitivity.hip): the instance's matrices from the fp32 record, and the exact discretisation
+// cmpc_sensitivity.hip, cmpc_gain.hip): the instance's matrices from the fp32 record, and the exact discretisation
 // in closed form. A_c^3 = 0 (ct_ss_mats, SolverMPC.cpp:260-279), so with N1 = dt A_c + dt^2/2 A_c^2
 //   Adt = I + N1,  Bdt = (dt I + dt^2/2 A_c + dt^3/6 A_c^2) B_c,  Qdt likewise with Q_c
 // exactly; each acts as a few sparse operations, stated here once.
@@ -48,7 +48,9 @@ __device__ __forceinline__ double bfly_max(double v) {
 // (SolverMPC.cpp:593; I_body = diag(ib0, ib1, ib2), the handle's model; RobotState.h:25 is the
 // default) in fp64 from the fp32 quaternion, the inverse by cofactors; x_drag, the Q_c f term and
 // x_0 beside them (the layout of scr above)
-__device__ __forceinline__ void rigid_setup(const float* __restrict__ rec, double ib0, double ib1, double ib2,
+// rigid_frame: R, I_world^-1 and x_drag alone (scr[0..18]): what Adt and Bdt are made of. It reads
+// the quaternion and x_drag words of the record and no other.
+__device__ __forceinline__ void rigid_frame(const float* __restrict__ rec, double ib0, double ib1, double ib2,
                                             double* scr) {
   const double qw = rec[CMPC_REC_Q + 0], qx = rec[CMPC_REC_Q + 1], qy = rec[CMPC_REC_Q + 2],
                qz = rec[CMPC_REC_Q + 3];
@@ -72,8 +74,12 @@ __device__ __forceinline__ void rigid_setup(const float* __restrict__ rec, doubl
   scr[9] = c00 * idet;  scr[10] = (Iw[2] * Iw[7] - Iw[1] * Iw[8]) * idet; scr[11] = (Iw[1] * Iw[5] - Iw[2] * Iw[4]) * idet;
   scr[12] = c10 * idet; scr[13] = (Iw[0] * Iw[8] - Iw[2] * Iw[6]) * idet; scr[14] = (Iw[2] * Iw[3] - Iw[0] * Iw[5]) * idet;
   scr[15] = c20 * idet; scr[16] = (Iw[1] * Iw[6] - Iw[0] * Iw[7]) * idet; scr[17] = (Iw[0] * Iw[4] - Iw[1] * Iw[3]) * idet;
-  const uint32_t flags = __float_as_uint(rec[CMPC_REC_FLAGS]);
   scr[18] = (double)rec[CMPC_REC_XDRAG];
+}
+__device__ __forceinline__ void rigid_setup(const float* __restrict__ rec, double ib0, double ib1, double ib2,
+                                            double* scr) {
+  rigid_frame(rec, ib0, ib1, ib2, scr);
+  const uint32_t flags = __float_as_uint(rec[CMPC_REC_FLAGS]);
   scr[19] = (flags & 1u) ? (double)rec[CMPC_REC_FEST3] : 0.0;  // Q_c f (SolverMPC.cpp:808-811)
   rpy_rounded(rec, &scr[20]);
 #pragma unroll
@@ -147,6 +153,24 @@ __device__ __forceinline__ N1Row n1_row(int jj, const double* scr, double dt, do
   if (jj == 5) { r.c11 = dt; r.c9 = dth * scr[18]; }
   if (jj == 11) r.c9 = dt * scr[18];
   return r;
+}
+// Column j of N1 as (row, value) pairs, at most three (columns 0..5 are empty; absent pairs are
+// (0, 0.0)): 6 + m rows 0..2 dt R[3 m + r]; 9 rows 3, 5, 11; 10 row 4; 11 row 5. With it X N1 and
+// N1'X cost three products per entry: (X N1)[i][c] = sum_t X[i][r_t(c)] v_t(c), (N1'X)[i][c] =
+// sum_t v_t(i) X[r_t(i)][c].
+struct N1Col { int r0, r1, r2; double v0, v1, v2; };
+__device__ __forceinline__ N1Col n1_col(int j, const double* scr, double dt, double dth) {
+  const double* R = scr;
+  N1Col c{0, 0, 0, 0.0, 0.0, 0.0};
+  if (j >= 6 && j < 9) {
+    const int m = j - 6;
+    c.r0 = 0; c.r1 = 1; c.r2 = 2;
+    c.v0 = dt * R[3 * m]; c.v1 = dt * R[3 * m + 1]; c.v2 = dt * R[3 * m + 2];
+  }
+  if (j == 9) { c.r0 = 3; c.r1 = 5; c.r2 = 11; c.v0 = dt; c.v1 = dth * scr[18]; c.v2 = dt * scr[18]; }
+  if (j == 10) { c.r0 = 4; c.v0 = dt; }
+  if (j == 11) { c.r0 = 5; c.v0 = dt; }
+  return c;
 }
 // Row jj of N1': its entries in columns 0..5 and 11 (rows 6..8 dt R lambda[0:3]; 9 dt (l3 +
 // x_drag l11) + dt^2/2 x_drag l5; 10 dt l4; 11 dt l5)

@@ -10,7 +10,7 @@
 //   0  forces, V and traj into LDS; R, I_world^-1 and x_0; Adt and Bdt dense (12 x 12 each)
 //   A  the step inputs d_k (evaluate's phases A, B), then x_k(U) - xd_k per step (its phase C)
 //   B  lane k: the face of step k's four foot-steps, a closed-form basis per foot-step, the columns
-//      of Z_k (at most 12) listed as (foot, three coefficients)
+//      of Z_k (at most 12) listed as (foot, three coefficients): face_columns, cmpc_face.h
 //   C  backwards over the steps, with Pn = P_k+1 + W and G = Bdt Z_k:
 //        R = alpha Z_k'Z_k + G'Pn G,  Cholesky,  K_k = R^-1 G'Pn Adt,  kappa_k = R^-1 (G'p_k+1 + Z_k'V_k / 2)
 //        P_k = Adt'Pn Adt - (Adt'Pn G) K_k,  p_k = Adt'p_k+1 - (Adt'Pn G) kappa_k
@@ -21,7 +21,7 @@
 #ifndef CMPC_SENSITIVITY_INST
 #define CMPC_SENSITIVITY_INST 0  // 1: the per-instance build (a second unit of this file, as cmpc_evaluate.hip's)
 #endif
-#include "cmpc_rigid64.h"
+#include "cmpc_face.h"
 
 namespace cmpc {
 namespace {
@@ -43,14 +43,6 @@ struct SensShared {
   unsigned char zf[12 * MAXN];  // column c of step k: its foot
   unsigned char dk[MAXN];       // columns of step k
 };
-
-// NaN-propagating minimum
-__device__ __forceinline__ double nmin(double a, double b) { return (a < b || a != a) ? a : b; }
-__device__ __forceinline__ double bfly_min(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = nmin(v, __shfl_xor(v, m, 64));
-  return v;
-}
 
 #if CMPC_SENSITIVITY_INST
 __global__ __launch_bounds__(64) void cmpc_sensitivity_inst_kernel(
@@ -169,59 +161,7 @@ __global__ __launch_bounds__(64) void cmpc_sensitivity_kernel(
   double mfree = 0.0, smin = __builtin_inf();
   if (lane < N) {
     const int k = lane;
-    const double mu_inv = (double)P.mu_inv;  // 1/mu as fmat holds it in fp32 (SolverMPC.cpp:657)
-    const double nrm = 1.0 / sqrt(mu_inv * mu_inv + 1.0);
-    const unsigned char* gait = reinterpret_cast<const unsigned char*>(rec + CMPC_REC_GAIT(N));
-    int col = 0;
-    for (int f = 0; f < 4; f++) {
-      const int t = 4 * k + f;
-      // ub(fz) = gait x f_max in fp32; swing (pinned) iff |ub| < 0.01, as every solver kernel tests
-      const float ubf = (float)gait[t] * P.f_max;
-      if (ubf < 0.01f && ubf > -0.01f) continue;
-      const double u0 = (double)sh.u[3 * t], u1 = (double)sh.u[3 * t + 1], u2 = (double)sh.u[3 * t + 2];
-      // the six rows of CMPC_CERT_VIOL, the friction rows normalised to unit length
-      const double s0 = (u0 * mu_inv + u2) * nrm, s1 = (-u0 * mu_inv + u2) * nrm;
-      const double s2 = (u1 * mu_inv + u2) * nrm, s3 = (-u1 * mu_inv + u2) * nrm;
-      const double s4 = u2, s5 = (double)ubf - u2;
-      const bool a0 = s0 <= act_tol, a1 = s1 <= act_tol, a2 = s2 <= act_tol, a3 = s3 <= act_tol;
-      const bool a4 = s4 <= act_tol, a5 = s5 <= act_tol;
-      if (!a0) smin = nmin(smin, s0);
-      if (!a1) smin = nmin(smin, s1);
-      if (!a2) smin = nmin(smin, s2);
-      if (!a3) smin = nmin(smin, s3);
-      if (!a4) smin = nmin(smin, s4);
-      if (!a5) smin = nmin(smin, s5);
-      // fz at 0, or both sides of an axis: the apex, nothing free
-      if (a4 || (a0 && a1) || (a2 && a3)) continue;
-      const bool sx = a0 || a1, sy = a2 || a3;
-      const double gx = a0 ? 1.0 : -1.0, gy = a2 ? 1.0 : -1.0;  // the active side's normal (g mu_inv, ., 1)
-      double z[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-      int d;
-      if (a5) {  // the cap: fz fixed
-        d = 0;
-        if (!sx && !sy) { z[0] = 1.0; z[1] = 0.0; z[2] = 0.0; z[3] = 0.0; z[4] = 1.0; z[5] = 0.0; d = 2; }
-        else if (sx && !sy) { z[0] = 0.0; z[1] = 1.0; z[2] = 0.0; d = 1; }
-        else if (!sx && sy) { z[0] = 1.0; z[1] = 0.0; z[2] = 0.0; d = 1; }
-      } else if (sx && sy) {  // an edge
-        z[0] = gx; z[1] = gy; z[2] = -mu_inv; d = 1;
-      } else if (sx) {
-        z[0] = 0.0; z[1] = 1.0; z[2] = 0.0; z[3] = 1.0; z[4] = 0.0; z[5] = -gx * mu_inv; d = 2;
-      } else if (sy) {
-        z[0] = 1.0; z[1] = 0.0; z[2] = 0.0; z[3] = 0.0; z[4] = 1.0; z[5] = -gy * mu_inv; d = 2;
-      } else {
-        z[0] = 1.0; z[1] = 0.0; z[2] = 0.0; z[3] = 0.0; z[4] = 1.0; z[5] = 0.0; z[6] = 0.0; z[7] = 0.0; z[8] = 1.0;
-        d = 3;
-      }
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        if (c >= d) break;
-        sh.zf[12 * k + col] = (unsigned char)f;
-        sh.zv[3 * (12 * k + col)] = z[3 * c];
-        sh.zv[3 * (12 * k + col) + 1] = z[3 * c + 1];
-        sh.zv[3 * (12 * k + col) + 2] = z[3 * c + 2];
-        col++;
-      }
-    }
+    const int col = face_columns(k, N, rec, sh.u, P, act_tol, &sh.zf[12 * k], &sh.zv[36 * k], smin);
     sh.dk[k] = (unsigned char)col;
     mfree = (double)col;
   }

@@ -37,6 +37,10 @@ CERT_WORDS = 8
 # dL/dweights [12], dL/dalpha, dL/df_est(3), the face's dimension, the smallest inactive slack
 SENS_X0, SENS_WEIGHTS, SENS_ALPHA, SENS_FEST3, SENS_FREE, SENS_SLACK = 0, 12, 24, 25, 26, 27
 SENS_WORDS = 32
+# words of a row of BatchSolver.gain (CMPC_GAIN_* of include/cmpc_solver.h): G [12 x 12] row-major, the
+# face's dimension over all steps, that of step 0, the smallest inactive slack
+GAIN_K, GAIN_FREE, GAIN_FREE0, GAIN_SLACK = 0, 144, 145, 146
+GAIN_WORDS = 148
 
 STATUS_NAMES = {0: "ok", 1: "max_iter", 2: "infeasible", 3: "not_pd", 4: "bad_input"}
 # locomotion-controller state for batched input assembly (include/cmpc_solver.h CMPC_LOCO_*)

@@ -25,7 +25,7 @@ from .records import COST_WORDS, make_instance_costs  # noqa: F401
 from .records import (CERT_COST, CERT_COST0, CERT_GAP, CERT_VIOL, CERT_SWING, CERT_GRADMAX,  # noqa: F401
                       CERT_WORDS, MAX_HORIZON)
 from .records import (SENS_X0, SENS_WEIGHTS, SENS_ALPHA, SENS_FEST3, SENS_FREE, SENS_SLACK,  # noqa: F401
-                      SENS_WORDS)
+                      SENS_WORDS, GAIN_K, GAIN_FREE, GAIN_FREE0, GAIN_SLACK, GAIN_WORDS)
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CMPC_LIB", os.path.join(PKG, "libcmpc_hip.so"))
@@ -92,6 +92,10 @@ _PROTOTYPES = {
     "cmpc_batch_sensitivity": (_int, [_vp, _vp, _vp, _vp, _int, _dbl, _vp, _vp, _vp]),
     "cmpc_batch_sensitivity_host": (_int, [_vp, _fp, _fp, _fp, _int, _dbl, _dp, _dp, _dp]),
     "cmpc_sensitivity_last": (_int, [_fp, _dbl, _dp, _dp, _dp]),
+    "cmpc_batch_gain": (_int, [_vp, _vp, _vp, _int, _dbl, _vp]),
+    "cmpc_batch_gain_host": (_int, [_vp, _fp, _fp, _int, _dbl, _dp]),
+    "cmpc_gain_last": (_int, [_dbl, _dp]),
+    "cmpc_batch_feedback": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp]),
     "cmpc_batch_enable_timing": (_int, [_vp, _int]),
     "cmpc_batch_enable_timing_every": (_int, [_vp, _int, _int]),
     "cmpc_batch_read_timing": (_int, [_vp, _fp, _ip, _ip]),
@@ -223,6 +227,15 @@ def sensitivity_last(grad_forces, act_tol: float = 1e-3):
                                      dtraj.ctypes.data_as(_dp), dg.ctypes.data_as(_dp)),
            "cmpc_sensitivity_last")
     return sens, dtraj[:n].reshape(-1, 12).copy(), dg[:n].copy()
+
+
+def gain_last(act_tol: float = 1e-3):
+    """``cmpc_gain_last``: the step-0 feedback gain of the last ``update_problem_data*`` call's solve
+    -> gain [GAIN_WORDS] float64 (G = gain[:144].reshape(12, 12)). Runs on request only; raises before
+    the first solve."""
+    gain = np.zeros(GAIN_WORDS, np.float64)
+    _check(load_library().cmpc_gain_last(float(act_tol), gain.ctypes.data_as(_dp)), "cmpc_gain_last")
+    return gain
 
 
 def set_f_ext(values) -> None:
@@ -515,6 +528,64 @@ class BatchSolver:
             o_traj.ctypes.data_as(_dp) if dtraj else None, o_dg.ctypes.data_as(_dp) if dg else None),
             "cmpc_batch_sensitivity_host")
         return sens, o_traj, o_dg
+
+    def gain(self, records, forces, gain, act_tol: float = 1e-3, batch: int | None = None) -> None:
+        """The step-0 feedback gain G = d u_0* / d x_0 by the fp64 Riccati recursion
+        (``cmpc_batch_gain``; asynchronous on the handle's stream): ``forces`` [B, 12N] float32 on
+        device, ``gain`` [B, GAIN_WORDS] float64 the output (indexed by ``GAIN_*``; G is the first 144
+        words, row-major [force component of step 0, component of x_0]). A row is active when its slack
+        is at most ``act_tol`` newtons. Checked as :meth:`sensitivity` checks its arguments."""
+        if batch is None:
+            batch = records.shape[0]
+        if batch > self.max_batch:
+            raise CmpcError(f"batch {batch} > max_batch {self.max_batch}")
+        n = 12 * self.horizon
+        if hasattr(records, "shape"):
+            assert records.shape[-1] == self.record_words, "record stride mismatch"
+        if hasattr(forces, "numel"):
+            assert forces.dtype.is_floating_point and forces.element_size() == 4, "forces must be float32"
+            assert forces.numel() >= batch * n
+        if hasattr(gain, "numel"):
+            assert gain.element_size() == 8 and gain.dtype.is_floating_point, "gain must be float64"
+            assert gain.numel() >= batch * GAIN_WORDS
+        _check(self.lib.cmpc_batch_gain(self._h, _ptr(records), _ptr(forces), int(batch), float(act_tol),
+                                        _ptr(gain)), "cmpc_batch_gain")
+
+    def gain_host(self, records: np.ndarray, forces: np.ndarray, act_tol: float = 1e-3) -> np.ndarray:
+        """Host arrays in/out (H2D + kernel + D2H, synchronous) -> gain [B, GAIN_WORDS] float64."""
+        records = np.ascontiguousarray(records, np.float32)
+        forces = np.ascontiguousarray(forces, np.float32)
+        B, n = records.shape[0], 12 * self.horizon
+        assert records.shape[1] == self.record_words and forces.size == B * n
+        gain = np.zeros((B, GAIN_WORDS), np.float64)
+        _check(self.lib.cmpc_batch_gain_host(self._h, records.ctypes.data_as(_fp), forces.ctypes.data_as(_fp), B,
+                                             float(act_tol), gain.ctypes.data_as(_dp)), "cmpc_batch_gain_host")
+        return gain
+
+    def feedback(self, records, forces, gain, states, u, due=None, batch: int | None = None) -> None:
+        """The held step-0 forces corrected for the present state, u = guard(u_0 + G (x - x_0))
+        (``cmpc_batch_feedback``; asynchronous on the handle's stream), all on device: ``forces`` float32
+        at the handle's output stride (``out_cols``), ``gain`` [B, GAIN_WORDS] float64 from
+        :meth:`gain`, ``states`` [B, 12] float32 in the order of the traj rows (rpy, p, w, v), ``u``
+        [B, 12] float32 the output. ``due`` [B] uint8 or None: an instance with a non-zero byte has just
+        been solved and is not written."""
+        if batch is None:
+            batch = records.shape[0]
+        if batch > self.max_batch:
+            raise CmpcError(f"batch {batch} > max_batch {self.max_batch}")
+        if hasattr(records, "shape"):
+            assert records.shape[-1] == self.record_words, "record stride mismatch"
+        for name, t, words in (("forces", forces, self.out_cols), ("states", states, 12), ("u", u, 12)):
+            if hasattr(t, "numel"):
+                assert t.dtype.is_floating_point and t.element_size() == 4, f"{name} must be float32"
+                assert t.numel() >= batch * words
+        if hasattr(gain, "numel"):
+            assert gain.element_size() == 8 and gain.dtype.is_floating_point, "gain must be float64"
+            assert gain.numel() >= batch * GAIN_WORDS
+        if hasattr(due, "numel"):
+            assert due.element_size() == 1 and due.numel() >= batch, "due must be [B] uint8"
+        _check(self.lib.cmpc_batch_feedback(self._h, _ptr(records), _ptr(forces), _ptr(gain), _ptr(states),
+                                            _ptr(due), int(batch), _ptr(u)), "cmpc_batch_feedback")
 
     def condense(self, records, H, g, batch: int | None = None, rows: bool = False) -> None:
         """Full (no elimination) qH [B,12N,12N] / qg [B,12N] on device — parity hook.
